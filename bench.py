@@ -1,9 +1,16 @@
 """Headline benchmark: Biscotti seconds per round (block commit) + final test accuracy,
 MNIST softmax regression, 100 peers (BASELINE.json; reference 29.83 s/round at 87.7%).
 
-    python bench.py --gpus N --steps K --warmup W [--config NAME]
+    python bench.py --gpus N --steps K --warmup W [--config NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K rounds and prints the result line; its accuracy fields are those of
+the last timed round.  ``--full`` adds what the headline figure does not need: the untimed rounds up to
+``--rounds`` (accuracy quoted the reference's way, after MAX_ITERATIONS = 100 rounds), the ``--seeds`` runs and
+the ledger's re-verification (``chain_valid``).  ``--dump-outputs DIR`` writes what the last timed round left a
+caller with (the global model, its test error and attack rate) as ``DIR/<name>.npy``; it stamps blocks with
+iteration + 1 (``--deterministic-time``), so the same arguments give the same inputs and chain run to run.
 
 Each step is one full protocol round with the reference defaults (3 verifiers, 3 aggregators,
 2 noisers, epsilon 2, ns 70%, secure aggregation + Multi-Krum + DP noising on): local SGD of all
@@ -161,6 +168,25 @@ def _spawn_ranks(n: int) -> int:
     return subprocess.call(cmd, env=dict(os.environ, OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", "4")))
 
 
+def _dump_outputs(out_dir: str, eng, results: list) -> None:
+    """What the timed rounds left a caller with, as float64 .npy files: the global model after the last timed
+    round (every rank holds the same one), that round's test error and attack rate, and the test error of
+    every timed round."""
+    import os
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    done = [r for r in results if r is not None]
+    last = done[-1] if done else None
+    arrays = {"global_w": eng.W.detach().to("cpu", torch.float64).numpy(),
+              "test_error": [last.test_error if last else float("nan")],
+              "attack_rate": [getattr(last, "attack_rate", float("nan")) if last else float("nan")],
+              "test_error_per_step": [r.test_error for r in done]}
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -183,9 +209,19 @@ def main() -> int:
     ap.add_argument("--deterministic-time", action="store_true",
                     help="block timestamps = iteration + 1 (RunConfig.deterministic_time): a seed's chain, and so "
                          "its accuracy curve, is the same run to run (--seeds experiments)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed rounds up to --rounds and the --seeds runs (accuracy after "
+                         "MAX_ITERATIONS rounds) and re-verify the ledger; a plain run only times its steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed round's outputs (global model, test error, attack rate) as "
+                         "DIR/<name>.npy; implies --deterministic-time")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.seeds > 1 and not a.full:
+        raise SystemExit("--seeds runs whole untimed runs: it needs --full")
+    if a.dump_outputs:
+        a.deterministic_time = True   # wall-clock block stamps are an input of the lottery: fixed, run to run
     import os
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -289,6 +325,8 @@ def main() -> int:
     elapsed = time.perf_counter() - t0
     drain_s = time.perf_counter() - t_drain
     drain_parts = dict(getattr(eng, "drain_parts_ms", None) or {})
+    if a.dump_outputs and comm.rank == 0:
+        _dump_outputs(a.dump_outputs, eng, results)   # before any untimed round moves the model on
     # device memory segments the caching allocator had to hipMalloc inside the timed window
     seg_new = (torch.cuda.memory_stats(comm.device).get("segment.all.allocated", 0) - seg0) if eng.gpu else 0
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
@@ -329,8 +367,9 @@ def main() -> int:
     accs = [1.0 - r.test_error for r in results]
     attacks = [r.attack_rate for r in results]
 
-    # accuracy is quoted the reference's way: after MAX_ITERATIONS = 100 rounds (untimed rounds finish
-    # the run when warmup + steps < 100), final value and last-10 mean, over --seeds runs
+    # --full: accuracy is quoted the reference's way: after MAX_ITERATIONS = 100 rounds (untimed rounds finish
+    # the run when warmup + steps < 100), final value and last-10 mean, over --seeds runs.  A plain run
+    # quotes the timed rounds it has: accuracy_rounds = warmup + steps
     def finish(e, acc_l, att_l, done):
         rs = []
         while done < a.rounds:
@@ -344,8 +383,9 @@ def main() -> int:
 
     all_acc = [[None] * a.warmup + accs]
     all_att = [[None] * a.warmup + attacks]
-    finish(eng, all_acc[0], all_att[0], a.warmup + a.steps)
-    for k in range(1, a.seeds):
+    if a.full:
+        finish(eng, all_acc[0], all_att[0], a.warmup + a.steps)
+    for k in range(1, a.seeds if a.full else 1):
         if hasattr(eng, "close"):
             eng.close()
         e2 = build(dataclasses.replace(cfg, seed=a.seed + k, trace_file=None))
@@ -361,13 +401,24 @@ def main() -> int:
             return None, None
         return float(st.mean(vals)), float(st.pstdev(vals)) if len(vals) > 1 else 0.0
 
-    R = a.rounds
-    finals = [l[R - 1] if len(l) >= R else l[-1] for l in all_acc]
-    last10 = [st.mean([v for v in l[max(0, min(R, len(l)) - 10):min(R, len(l))] if v is not None]) for l in all_acc]
-    att_final = [l[R - 1] if len(l) >= R else l[-1] for l in all_att]
-    att10 = [st.mean([v for v in l[max(0, min(R, len(l)) - 10):min(R, len(l))] if v is not None]) for l in all_att]
+    R = a.rounds if a.full else a.warmup + a.steps
+
+    def final_of(l):
+        return l[R - 1] if len(l) >= R > 0 else l[-1] if l else None
+
+    def last10_of(l):
+        vals = [v for v in l[max(0, min(R, len(l)) - 10):min(R, len(l))] if v is not None]
+        return st.mean(vals) if vals else None
+
+    finals = [final_of(l) for l in all_acc]
+    last10 = [last10_of(l) for l in all_acc]
+    att_final = [final_of(l) for l in all_att]
+    att10 = [last10_of(l) for l in all_att]
     acc = finals[0]
-    ok, why = eng.fsm.chain.verify() if not fedsys else (True, "")
+    # the ledger's re-verification walks every block again: a check of its own, not the headline's (--full)
+    ok = None
+    if a.full:
+        ok, why = eng.fsm.chain.verify() if not fedsys else (True, "")
     # contributors per committed block (updates in the block; the reference's churn logs show it as the stake
     # map's growth: stake_unit per contributor) and the stake total, for the churn comparisons
     blocks = len(eng.fsm.chain) - 1 if not fedsys else None
@@ -443,7 +494,9 @@ def main() -> int:
                        "noising": cfg.noising, "fedsys": fedsys},
             "phase_ms_per_round": {k: 1e3 * v / max(a.steps, 1) for k, v in sorted(phases.items())},
             "phase_sync": bool(a.phase_sync),
-            "chain_valid": bool(ok),
+            "full": bool(a.full),
+            "dumped_outputs": a.dump_outputs,
+            "chain_valid": bool(ok) if ok is not None else None,   # None: not checked (plain run)
             "miner_threshold": getattr(cfg, "miner_threshold", None),
             "leader_cap": eng.fsm.leader_cap_size() if not fedsys else None,
             "contributors_per_block": contrib,

@@ -42,8 +42,8 @@ def main() -> int:
     a = ap.parse_args()
     with open(a.out, "a") as f:
         for args, tag in SWEEPS[a.sweep]:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup",
-                   str(a.warmup), *args]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(a.steps), "--warmup",
+                   str(a.warmup), *args]   # --full: the points are compared by their 100-round accuracy too
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout, cwd=ROOT)
             except subprocess.TimeoutExpired:

@@ -11,10 +11,10 @@
 #   long                  200 timed rounds
 #   emuN[xK]              K driver-style runs of rank 0 of an N-rank job (bench.py --emulate-world N)
 #   rehN[:ROUNDS]         an N-rank RCCL rehearsal, every rank on the one GPU (default 60 rounds)
-#   cfg:NAME[:STEPS]      a bench preset (bench.py --config NAME)
+#   cfg:NAME[:STEPS]      a bench preset with its 100-round accuracy (bench.py --full --config NAME)
 #   bench:TAG:A+B+C       bench.py with arguments A B C ('+' separates them), output OUT/TAG.txt
 #   set:K=V[,K=V][xK]     driver-style runs with --set K=V ... (A/B ablations)
-#   seeds:NAME:N          bench.py --config NAME --seeds N (accuracy over seeds)
+#   seeds:NAME:N          bench.py --full --config NAME --seeds N (accuracy over seeds)
 #   prof                  rocprofv3 --kernel-trace --stats of a driver-style run (OUT/prof/)
 #   hosttl[:N|w:N]        the host timeline of 4 steady rounds (scripts/host_timeline.py; :N emulated rank 0 of N,
 #                         w:N the same with 100 peers per rank)
@@ -77,14 +77,14 @@ for step in "$@"; do
       bench "$tag" 900 "${args[@]}" ;;
     cfg:*)
       s="${step#cfg:}"; name="${s%%:*}"; st=20; [[ "$s" == *:* ]] && st="${s#*:}"
-      bench "cfg_$name" 900 --config "$name" --steps "$st" --warmup 5 ;;
+      bench "cfg_$name" 900 --full --config "$name" --steps "$st" --warmup 5 ;;
     set:*)
       s="${step#set:}"; kv="${s%%x*}"; args=()
       IFS=',' read -ra kvs <<< "$kv"; for x in "${kvs[@]}"; do args+=(--set "$x"); done
       for i in $(seq 1 "$(reps "$step")"); do bench "set_${kv//[=,]/_}_s$i" 300 --steps 20 --warmup 5 "${args[@]}"; done ;;
     seeds:*)
       s="${step#seeds:}"; name="${s%%:*}"; k="${s#*:}"
-      timeout -k 10 1100 python bench.py --config "$name" --seeds "$k" > "$O/seeds_$name.txt" 2>&1 \
+      timeout -k 10 1100 python bench.py --full --config "$name" --seeds "$k" > "$O/seeds_$name.txt" 2>&1 \
         || { echo "FAIL seeds $name"; tail -20 "$O/seeds_$name.txt"; exit 1; }
       grep '^{' "$O/seeds_$name.txt" | tail -1 | head -c 600; echo ;;
     prof)

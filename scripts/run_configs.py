@@ -24,8 +24,8 @@ def main() -> int:
     rc_all = 0
     with open(a.out, "a") as f:
         for c in a.configs:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", c, "--steps", str(a.steps),
-                   "--warmup", str(a.warmup)]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", c, "--steps", str(a.steps),
+                   "--warmup", str(a.warmup)]   # --full: each preset's 100-round accuracy and chain check
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout, cwd=ROOT)
             except subprocess.TimeoutExpired:

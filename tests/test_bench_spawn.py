@@ -13,7 +13,7 @@ def test_bench_spawns_ranks_and_reports_them():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PYTHONPATH"] = ROOT
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "credit4", "--steps", "2",
-                        "--warmup", "1", "--rounds", "3"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--warmup", "1", "--rounds", "3", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,7 +96,7 @@ def test_bench_emulate_world_runs_rank0_alone():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PYTHONPATH"] = ROOT
     r = subprocess.run([sys.executable, "bench.py", "--emulate-world", "4", "--config", "credit4", "--steps", "3",
-                        "--warmup", "1", "--rounds", "4"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--warmup", "1", "--rounds", "4", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

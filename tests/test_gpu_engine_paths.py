@@ -211,7 +211,7 @@ def test_mnist_label_flip_rejection_floor_default_noise():
 
 
 # this deterministic run measures 0.647 (rejection 0.756); the reproducible 5-seed poison30 run (bench.py
-# --deterministic-time --seeds 5, round 6) gives 0.582 +- 0.065 with a worst seed of 0.644: ceiling 0.70
+# --full --deterministic-time --seeds 5, round 6) gives 0.582 +- 0.065 with a worst seed of 0.644: ceiling 0.70
 DIGIT1_ERR_CEILING = 0.70
 
 

@@ -208,7 +208,8 @@ def test_gpu_emulated_rank0_native_collectives():
     import json
 
     out = subprocess.run([sys.executable, "bench.py", "--emulate-world", "4", "--steps", "4", "--warmup", "2",
-                          "--rounds", "8", "--peers", "24"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--rounds", "8", "--peers", "24", "--full"], cwd=ROOT, capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads(next(ln for ln in out.stdout.splitlines() if ln.startswith("{")))
     st = rec["engine_stats"]

@@ -46,13 +46,39 @@ def test_engine_log_lines_parse(tmp_path):
 
 def test_bench_cpu_credit4_and_set_override():
     out = subprocess.run([sys.executable, "bench.py", "--config", "credit4", "--steps", "3", "--warmup", "1",
-                          "--set", "seed=7"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--set", "seed=7", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads(next(ln for ln in out.stdout.splitlines() if ln.startswith("{")))
     assert rec["config"]["name"] == "credit4" and rec["chain_valid"] and rec["steps"] == 3
     for k in ("metric", "value", "unit", "n_gpus", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config"):
         assert k in rec
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full) stops after its timed rounds: no untimed rounds, no ledger re-verification; and
+    --dump-outputs writes the last timed round's model and evaluation, the same bits for the same arguments."""
+    import numpy as np
+
+    recs, dumps = [], []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, "bench.py", "--config", "credit4", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        recs.append(json.loads(next(ln for ln in out.stdout.splitlines() if ln.startswith("{"))))
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    rec = recs[0]
+    assert rec["full"] is False and rec["chain_valid"] is None
+    assert rec["steps"] == 3 and rec["rounds_total"] == 4 and rec["accuracy_rounds"] == 4
+    assert len(rec["round_wall_ms"]) == 3 and abs(rec["ms_per_step"] - 1e3 * rec["value"]) < 1e-9
+    assert rec["deterministic_time"] is True
+    a, b = dumps
+    assert sorted(a) == ["attack_rate", "global_w", "test_error", "test_error_per_step"]
+    assert a["global_w"].shape == (25,) and a["test_error_per_step"].shape == (3,)
+    assert np.abs(a["global_w"]).max() > 0 and abs((1.0 - a["test_error"][0]) - rec["final_test_acc"]) < 1e-12
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k], equal_nan=True), k
 
 
 def test_sandbox_models_train_on_cpu():
@@ -186,7 +212,7 @@ def test_bench_scale_weak_preset_four_gloo_ranks():
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
                           "--master-addr=127.0.0.1", f"--master-port={port}", "bench.py", "--gpus", "4",
-                          "--config", "scale_weak", "--steps", "2", "--warmup", "1", "--rounds", "3",
+                          "--config", "scale_weak", "--steps", "2", "--warmup", "1", "--rounds", "3", "--full",
                           "--set", "dataset=creditcard", "--set", "noising=false", "--set", "host_threads=2"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

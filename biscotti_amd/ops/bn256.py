@@ -159,6 +159,29 @@ class DeviceCommitEngine:
                "shares_msm")
         return pts, ys
 
+    def shares_ka(self, coeffs: torch.Tensor, rows_host: np.ndarray, commit_only: int = 0,
+                  alive: torch.Tensor | None = None, group_rows: int = 0):
+        """shares() through the kernel the round runs: the row list (host int32 [n], n <= 248) travels in the
+        kernel's argument block instead of device memory.  Same outputs as shares(); no compaction."""
+        assert coeffs.dtype == torch.int64 and coeffs.dim() == 2 and coeffs.shape[1] == self.d
+        assert isinstance(rows_host, np.ndarray) and rows_host.dtype == np.int32 and rows_host.ndim == 1
+        rows_host = np.ascontiguousarray(rows_host)
+        n = rows_host.size
+        if n:
+            assert int(rows_host.min()) >= 0 and int(rows_host.max()) < coeffs.shape[0], "row index out of range"
+        commit_only = int(commit_only)
+        S = 1 if commit_only == 1 else self.T + 1
+        pts = torch.empty((n, self.nchunks, S, 24), dtype=torch.int32, device=self.device)
+        ys = None if commit_only == 1 else torch.empty((n, self.nchunks, self.T), dtype=torch.int64,
+                                                       device=self.device)
+        if alive is not None:
+            assert alive.dtype == torch.int32 and alive.numel() == n
+        _check(hip().bsc_shares_msm_ka(_ptr(coeffs), self.d, rows_host.ctypes.data, n, _ptr(self.tbl_pk),
+                                       _ptr(self.tbl_wb), self.poly, self.T, self.b0, self.nw, commit_only,
+                                       _ptr(alive), int(group_rows), _ptr(pts), _ptr(ys), _stream()),
+               "shares_msm_ka")
+        return pts, ys
+
     def commit_rows(self, coeffs: torch.Tensor, rows: torch.Tensor, check_rows: bool = True) -> torch.Tensor:
         """Full-vector commitments sum_i c_i PK[i] of the given rows, Jacobian [n, 24] (commit phase)."""
         assert coeffs.dtype == torch.int64 and coeffs.dim() == 2 and coeffs.shape[1] == self.d

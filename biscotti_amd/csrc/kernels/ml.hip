@@ -1147,6 +1147,102 @@ extern "C" __global__ void __launch_bounds__(64) k_eval_finish(unsigned int* err
 }
 
 // =====================================================================================
+// Committee RONI (VerifyUpdateRONI, main.go:191-233): every local verifier's minibatch scored under the base
+// model and under W + U[c] for every row c of its inbox, in ONE launch.  counts[v][0] = #misclassified
+// minibatch rows of verifier v under W; counts[v][1 + j] the same under W + U[cand[v][j]].
+// One block per (column, verifier, 16-row tile of the minibatch).  The arithmetic is k_eval_error's, step for
+// step (K partition over the 4 waves, the two accumulators, the guarded tail, the LDS reduction order, the bias
+// add, the first-maximum argmax), with the B operand (float)(W[k] + (double)U[c][k]) formed in registers -- what
+// the host loop's `W + X[i].double()` followed by k_eval_error's (float)wr[k] gives -- so the logits, and with
+// them the counts, are bit-identical to one k_eval_error launch per (verifier, candidate).  The minibatch rows
+// are gathered by index (rows: absolute rows of X); slots past nrows[v] load a clamped row and are not counted.
+// =====================================================================================
+extern "C" __global__ void __launch_bounds__(256) k_roni_counts(const float* X, const int* y, long long NX, int D_IN,
+                                                               int D_OUT, const double* W, const float* U, int n_cand,
+                                                               const long long* rows, const int* nrows, int Bmax,
+                                                               const int* cand, int ni, int transform,
+                                                               unsigned int* counts) {
+  __shared__ float red[4][4][64];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int col = blockIdx.x, v = blockIdx.y, row0 = blockIdx.z * 16;
+  const int nr = min(nrows[v], Bmax);
+  if (row0 >= nr) return;  // the whole block: no barrier is skipped by part of it
+  const int i = lane & 15, kk = lane >> 4;
+  const long long* rv = rows + (size_t)v * Bmax;
+  const long long gr = min(max(rv[min(row0 + i, nr - 1)], 0ll), NX - 1);
+  const float* xr = X + (size_t)gr * D_IN;
+  const bool cval = i < D_OUT;
+  const size_t wo = (size_t)(cval ? i : 0) * D_IN;
+  const double* wr = W + wo;
+  // column 0 is the base model; an inbox slot without a row (cand < 0 or past U) is scored as the base model
+  const int c = col > 0 ? cand[(size_t)v * ni + (col - 1)] : -1;
+  const bool upd = c >= 0 && c < n_cand;
+  const size_t D = (size_t)D_OUT * D_IN + D_OUT;
+  const float* uc = U + (upd ? (size_t)c * D : 0);
+  const float* ur = uc + wo;
+  const float tsub = transform ? 0.5f : 0.f, tmul = transform ? 2.f : 1.f;
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  const int kq = ((D_IN + 15) / 16) * 4;  // this wave's K range: multiple of 4
+  int k0 = wid * kq;
+  const int kend = min(D_IN, k0 + kq);
+  for (; k0 + 32 <= kend; k0 += 32) {
+    float a[8], b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = k0 + 4 * u + kk;
+      a[u] = xr[k];
+      b[u] = cval ? (upd ? (float)(wr[k] + (double)ur[k]) : (float)wr[k]) : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; u += 2) {
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32((a[u] - tsub) * tmul, b[u], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32((a[u + 1] - tsub) * tmul, b[u + 1], acc1, 0, 0, 0);
+    }
+  }
+  for (; k0 < kend; k0 += 4) {
+    const int k = k0 + kk;
+    const bool in = k < kend;
+    const float a = in ? (xr[k] - tsub) * tmul : 0.f;
+    const float b = (in && cval) ? (upd ? (float)(wr[k] + (double)ur[k]) : (float)wr[k]) : 0.f;
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc0, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc0[r] + acc1[r];
+  __syncthreads();
+  if (wid != 0) return;
+  const size_t bo = (size_t)D_OUT * D_IN + (cval ? i : 0);
+  const float bias = cval ? (upd ? (float)(W[bo] + (double)uc[bo]) : (float)W[bo]) : 0.f;
+  unsigned int cnt = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    // D layout of 16x16x4 f32: lane l holds D[row (l>>4)*4 + r][class l&15]
+    const float logit = (red[0][r][lane] + red[1][r][lane]) + (red[2][r][lane] + red[3][r][lane]);
+    float bv = cval ? logit + bias : -__builtin_huge_valf();
+    int bc = i;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 16);
+      const int oc = __shfl_xor(bc, o, 16);
+      if (ov > bv || (ov == bv && oc < bc)) {
+        bv = ov;
+        bc = oc;
+      }
+    }
+    const int row = row0 + kk * 4 + r;
+    if (i == 0 && row < nr && bc != y[min(max(rv[row], 0ll), NX - 1)]) ++cnt;
+  }
+  // the four row groups' counts (lanes 0, 16, 32, 48) into lane 0: one store per block, or one atomic when the
+  // minibatch spans several tiles (the counters are zeroed before the launch)
+  cnt += __shfl_xor(cnt, 16);
+  cnt += __shfl_xor(cnt, 32);
+  if (lane == 0) {
+    unsigned int* out = counts + (size_t)v * (ni + 1) + col;
+    if (Bmax <= 16) *out = cnt;
+    else if (cnt) atomicAdd(out, cnt);
+  }
+}
+
+// =====================================================================================
 // K12: exact recovery of the aggregated chunk polynomials from miner shares.
 // ys: int64 [nchunks][npts], xs: int [npts] distinct; deg+1 <= npts.  Newton divided differences
 // in 128-bit on the deg+1 nodes of smallest |x|, verified against every share.  Writes the
@@ -1607,6 +1703,27 @@ extern "C" int bsc_eval_error_t_rb(const float* Xt, const int* y, int N, int KG,
                      W, split, err, err_host);
   hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, err, err_host);
   return (int)hipGetLastError();
+}
+
+// committee RONI: counters zeroed, k_roni_counts, and the [V, ni + 1] counts' read-back into pinned memory, all on
+// `stream`.  ni == 0 scores the base model only (one column).  No verifier or no minibatch slot: nothing is launched
+// (the host buffer is not written).
+extern "C" int bsc_roni_counts_rb(const float* X, const int* y, long long NX, int D_IN, int D_OUT, const double* W,
+                                  const float* U, int n_cand, const long long* rows, const int* nrows, int V, int Bmax,
+                                  const int* cand, int ni, int transform, unsigned int* counts,
+                                  unsigned int* counts_host, void* stream) {
+  if (D_OUT > 16 || D_OUT <= 0 || D_IN <= 0 || ni < 0) return -1;
+  if (V <= 0 || Bmax <= 0) return 0;
+  const int tiles = (Bmax + 15) / 16;
+  if (NX <= 0 || V > 65535 || tiles > 65535 || (ni > 0 && n_cand <= 0)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)V * (ni + 1) * sizeof(unsigned int);
+  if (hipMemsetAsync(counts, 0, bytes, s) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_roni_counts, dim3(ni + 1, V, tiles), dim3(256), 0, s, X, y, NX, D_IN, D_OUT, W, U, n_cand, rows,
+                     nrows, Bmax, cand, ni, transform, counts);
+  const int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  return (int)hipMemcpyAsync(counts_host, counts, bytes, hipMemcpyDeviceToHost, s);
 }
 
 extern "C" int bsc_noise_table(int nnoisers, int D, unsigned long long seed, float* tbl, void* stream) {

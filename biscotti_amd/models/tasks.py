@@ -108,6 +108,25 @@ class SoftmaxTask:
         sel = h2d([o + r for r in rows], torch.long, self.device)
         return K.eval_error(self.X[sel].contiguous(), self.y[sel].contiguous(), W, self.d_in, self.d_out, True)
 
+    def roni_rows(self, verifiers: list[int], iteration: int):
+        """The minibatches train_error draws for the listed local verifiers, as host arrays for the committee
+        kernel (K.roni_committee_async): rows int64 [V, batch] -- absolute rows of self.X, a shard shorter than the
+        batch padded with its last drawn row -- and nrows int32 [V], the valid rows of each."""
+        c = self.__dict__.get("_shard_np")
+        if c is None:   # the shard table on the host (read once: off / ntrain never change)
+            c = self._shard_np = (self.off.cpu().numpy(), self.ntrain.cpu().numpy())
+        rows = np.zeros((len(verifiers), self.batch), np.int64)
+        nrows = np.zeros((len(verifiers),), np.int32)
+        for k, peer in enumerate(verifiers):
+            i = self._local_index[peer]
+            o, n = int(c[0][i]), int(c[1][i])
+            idx = K.minibatch_indices(peer, iteration, n, self.batch, self.seed ^ 0xB0B)
+            nrows[k] = len(idx)
+            if idx:
+                rows[k, :len(idx)] = np.asarray(idx, np.int64) + o
+                rows[k, len(idx):] = rows[k, len(idx) - 1]
+        return rows, nrows
+
 
 class LogisticTask:
     """creditcard logistic regression: every peer loads the full dataset (logistic_model.py:26)."""

@@ -710,6 +710,75 @@ def eval_error(X, y, W, d_in, d_out, transform=True) -> float:
     return float((pred != y.long()).sum()) / N
 
 
+# ---------------------------------------------------------------------------- committee RONI
+_RONI_DEV: dict = {}   # pinned read-back buffer -> its device counters (persistent pairs)
+
+
+def roni_committee_async(X, y, rows, nrows, W, U, cand, d_in, d_out, transform=True):
+    """Every verifier's RONI error counts from ONE kernel launch and one read-back (k_roni_counts).
+
+    X fp32 [N, d_in], y int32 [N]: the resident training rows; rows int64 [V, Bmax]: absolute rows of X of each
+    verifier's minibatch, nrows int32 [V] of them valid; W fp64 [nparam]; U fp32 [n_cand, nparam]: the candidate
+    updates; cand int32 [V, ni]: the row of U in each inbox slot.  Returns a callable giving counts, a numpy
+    uint32 [V, ni + 1]: column 0 the misclassified minibatch rows under W, column 1 + j under W + U[cand[v, j]]
+    -- the counts eval_error gives per (verifier, model), bit for bit.  ni == 0 gives the base column alone; with
+    no verifier or no minibatch slot the counts are zeros and nothing is launched."""
+    V, Bmax = rows.shape
+    ni = cand.shape[1] if cand.dim() == 2 else 0
+    nparam = d_out * d_in + d_out
+    if V == 0 or Bmax == 0:
+        z = np.zeros((V, ni + 1), np.uint32)
+        return lambda: z
+    if X.device.type != "cuda":
+        counts = np.zeros((V, ni + 1), np.uint32)
+        nr, cd = nrows.tolist(), cand.tolist()
+        for v in range(V):
+            n = min(nr[v], Bmax)
+            if n <= 0:
+                continue
+            sel = rows[v, :n].long()
+            Xv, yv = X[sel].contiguous(), y[sel].contiguous()
+            models = [W] + [W + U[c].double() for c in (cd[v] if ni else [])]
+            for j, Wm in enumerate(models):
+                counts[v, j] = round(eval_error(Xv, yv, Wm, d_in, d_out, transform) * n)
+        return lambda: counts
+    assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+    assert rows.dtype == torch.int64 and nrows.dtype == torch.int32 and nrows.numel() == V
+    assert X.shape[1] == d_in and W.numel() == nparam
+    if ni:
+        assert U.dtype == torch.float32 and cand.dtype == torch.int32 and U.shape[1] == nparam and cand.shape[0] == V
+    # the pinned buffer rotates (a committee's counts may still be unread when the next is queued); its device
+    # counters rotate with it
+    host = pinned("roni", (V, ni + 1), torch.int32, depth=4)
+    dev = _RONI_DEV.get(host.data_ptr())
+    if dev is None:
+        dev = _RONI_DEV[host.data_ptr()] = torch.zeros((V, ni + 1), dtype=torch.int32, device=X.device)
+    _check(hip().bsc_roni_counts_rb(_p(X), _p(y), X.shape[0], d_in, d_out, _p(W), _p(U) if ni else None,
+                                    U.shape[0] if ni else 0, _p(rows), _p(nrows), V, Bmax, _p(cand) if ni else None,
+                                    ni, int(transform), _p(dev), host.data_ptr(), _stream()), "roni_counts")
+    ev = S.record()
+
+    def result():
+        S.host_wait(ev)
+        return host.numpy().view(np.uint32).copy()
+    result.ready = ev.query
+    return result
+
+
+def roni_committee(X, y, rows, nrows, W, U, cand, d_in, d_out, transform=True) -> np.ndarray:
+    """roni_committee_async, read back at once: counts uint32 [V, ni + 1]."""
+    return roni_committee_async(X, y, rows, nrows, W, U, cand, d_in, d_out, transform)()
+
+
+def roni_accept(counts, nrows, threshold: float = 0.02) -> np.ndarray:
+    """RONI's decision from the committee's counts: bool [V, ni], slot j of verifier v accepted iff its training
+    error under the update exceeds the base model's by at most `threshold` (VerifyUpdateRONI, main.go:191-233) --
+    in float64, the arithmetic of `train_error(W + u) - train_error(W) <= 0.02`."""
+    c = np.asarray(counts, np.float64)
+    n = np.asarray(nrows, np.float64).reshape(-1, 1)
+    return (c[:, 1:] / n - c[:, :1] / n) <= threshold
+
+
 # ---------------------------------------------------------------------------- K12 recovery
 def recover(agg_y, xs, poly: int, d: int, W, qscale=1e4):
     """Recover the aggregated quantised update from miner shares and apply it to W.

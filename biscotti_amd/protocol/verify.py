@@ -230,6 +230,26 @@ class VerifyMixin:
         acc, _ = K.krum(X, n - clip, n - clip)
         return [bool(a) for a in acc.cpu().tolist()]
 
+    def _roni_committee(self, X: torch.Tensor, xrow, inboxes: dict, local_vs: list, it: int):
+        """RONI for every local verifier at once (k_roni_counts): each verifier's minibatch under W and under
+        W + every row of its inbox in ONE launch with one read-back, instead of _verify's launch and wait per
+        (verifier, candidate).  The same error counts bit for bit, so the same decisions.  X: the candidate
+        rows, xrow: worker -> row of X.  Returns bool [len(local_vs), ni], or None where it does not apply (CPU,
+        a task without roni_rows such as creditcard, the collusion experiment, no local verifier): the caller
+        then takes the _verify loop."""
+        if not (self.gpu and local_vs and self.cfg.colluders == 0 and hasattr(self.task, "roni_rows")):
+            return None
+        rows_np, nrows_np = self.task.roni_rows(local_vs, it)
+        if not nrows_np.all():   # an empty shard: train_error's 0.0 convention stays with the loop
+            return None
+        cand_np = np.asarray([[xrow[w] for w in inboxes[v]] for v in local_vs], np.int32)
+        rows, nrows, cand = h2d_many([(rows_np, torch.int64), (nrows_np, torch.int32), (cand_np, torch.int32)],
+                                     self.dev)
+        with self.timer.phase("verify.defense"):
+            counts = K.roni_committee_async(self.task.X, self.task.y, rows, nrows, self.W, X.contiguous(), cand,
+                                            self.task.d_in, self.task.d_out)()
+        return K.roni_accept(counts, nrows_np)
+
     # ------------------------------------------------------------------ the verification phase
     def _vgather(self):
         """The packed verification gather (ops/gather.py) for several ranks on GPUs with the noise-aware Krum,
@@ -446,8 +466,13 @@ class VerifyMixin:
                 # RONI: each verifier judges with its own data, so only its rank can decide; the accept
                 # matrix [nv, ni] travels in one all_gather on several ranks
                 mine = np.zeros((nv, ni), np.uint8)
-                for v in vs:
-                    if v in self.local:
+                local_vs = [v for v in vs if v in self.local]
+                ok_all = self._roni_committee(X, xrow, inboxes, local_vs, it)   # one launch, one read-back
+                if ok_all is not None:
+                    for k, v in enumerate(local_vs):
+                        mine[plan.verifiers.index(v)] = ok_all[k]
+                else:   # CPU, creditcard, the collusion experiment: one verifier and one candidate at a time
+                    for v in local_vs:
                         rows_v = h2d([xrow[w] for w in inboxes[v]], torch.long, self.dev)
                         with tm.phase("verify.defense"):
                             ok = self._verify(X.index_select(0, rows_v), inboxes[v], it, v)

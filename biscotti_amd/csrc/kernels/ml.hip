@@ -457,6 +457,7 @@ extern "C" __global__ void __launch_bounds__(128) k_krum_accept(const double* sc
 //                        split K further and reduce through LDS -> part[split][pair][16][16]
 //   KC2 k_krum_rows      one block per (inbox row, verifier): D_ij from the (deterministically
 //                        reduced) Gram, rank-select of the groupsize-2 nearest neighbours, score
+//                        (krum_rows_body; k_krum_rows_noise / _ka are the same body on another inner product)
 //   KC3 k_krum_vote      one block: per-verifier selection of the n_accept lowest scores, signature
 //                        count per worker row, approval (>= need), leader cap by arrival rank
 // Limits: U <= 1024 rows, inbox n <= 256 on this path; larger committees take the *_big kernels below.
@@ -580,40 +581,6 @@ extern "C" __global__ void __launch_bounds__(256) k_gram_reduce(const double* pa
   gram[(size_t)pair * 256 + e] = g;
 }
 
-extern "C" __global__ void __launch_bounds__(256) k_krum_rows(const double* gram, int T, const int* inbox, int n,
-                                                             int groupsize, double* scores) {
-  __shared__ double row[256];
-  __shared__ double kept[256];
-  __shared__ double gdiag_a;
-  const int i = blockIdx.x, v = blockIdx.y, t = threadIdx.x;
-  const int* box = inbox + (size_t)v * n;
-  const int a = box[i];
-  if (t == 0) gdiag_a = gram_at(gram, T, a, a);
-  __syncthreads();
-  if (t < n) {
-    const int b = box[t];
-    const double gab = gram_at(gram, T, a, b);
-    const double gbb = gram_at(gram, T, b, b);
-    row[t] = gdiag_a + gbb - 2.0 * gab;
-  }
-  __syncthreads();
-  if (t < n) {
-    const double val = row[t];
-    int rank = 0;
-    for (int k2 = 0; k2 < n; ++k2) {
-      const double u = row[k2];
-      rank += (u < val) || (u == val && k2 < t);
-    }
-    kept[t] = (rank >= 1 && rank < groupsize - 1) ? val : 0.0;
-  }
-  __syncthreads();
-  if (t == 0) {
-    double s = 0.0;
-    for (int j = 0; j < n; ++j) s += kept[j];
-    scores[(size_t)v * n + i] = s;
-  }
-}
-
 // KC2, noise-aware form: the candidate rows are x_a = delta_a + (1/nn) sum_s sc[a][s] t_{nz[a][s]}
 // (the noisers' pre-sampled vectors, main.go:1592-1660), and the Gram was taken over the stacked
 // [deltas; noise vectors] rows, so <x_a, x_b> expands into (1 + nn)^2 Gram entries -- the
@@ -653,27 +620,39 @@ __device__ __forceinline__ double xx_dot(const double* gram, int T, int U1, N q,
            gram_at(gram, T, U1 + q.nz(a * nn + s2), U1 + q.nz(b * nn + t));
   return v;
 }
-// wrapper kept for k_krum_rows_big (device arrays)
-__device__ __forceinline__ double xx_dot(const double* gram, int T, int U1, const int* nz, const float* sc, int nn,
-                                         int a, int b) {
-  return xx_dot(gram, T, U1, NoisePtr{nz, sc}, nn, a, b);
-}
 
+// the inner product <x_a, x_b> of two candidate rows, in its two forms: a Gram entry, or the noise-aware assembly
+struct PlainDot {
+  const double* gram;
+  int T;
+  __device__ __forceinline__ double operator()(int a, int b) const { return gram_at(gram, T, a, b); }
+};
 template <class N>
-__device__ __forceinline__ void krum_rows_noise_body(const double* gram, int T, int U1, N q, int nn, const int* inbox,
-                                                     int n, int groupsize, double* scores) {
+struct NoiseDot {
+  const double* gram;
+  int T, U1;
+  N q;
+  int nn;
+  __device__ __forceinline__ double operator()(int a, int b) const { return xx_dot(gram, T, U1, q, nn, a, b); }
+};
+
+// KC2, every form: block (i, v) scores row i of verifier v's inbox.  Thread t holds the squared distance
+// <a,a> + <b,b> - 2 <a,b> to inbox row t (<a,a> once per block), ranks it among the row's distances (index
+// tie-break) and keeps it when 1 <= rank < groupsize - 1; thread 0 sums the kept values serially in inbox order
+// (the f64 summation order the accept masks depend on)
+template <class Dot>
+__device__ __forceinline__ void krum_rows_body(Dot dot, const int* inbox, int n, int groupsize, double* scores) {
   __shared__ double row[256];
-  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
   __shared__ double kept[256];
   __shared__ double xaa;
   const int i = blockIdx.x, v = blockIdx.y, t = threadIdx.x;
   const int* box = inbox + (size_t)v * n;
   const int a = box[i];
-  if (t == 0) xaa = xx_dot(gram, T, U1, q, nn, a, a);
+  if (t == 0) xaa = dot(a, a);
   __syncthreads();
   if (t < n) {
     const int b = box[t];
-    row[t] = xaa + xx_dot(gram, T, U1, q, nn, b, b) - 2.0 * xx_dot(gram, T, U1, q, nn, a, b);
+    row[t] = xaa + dot(b, b) - 2.0 * dot(a, b);
   }
   __syncthreads();
   if (t < n) {
@@ -694,17 +673,25 @@ __device__ __forceinline__ void krum_rows_noise_body(const double* gram, int T, 
 }
 }  // namespace
 
+extern "C" __global__ void __launch_bounds__(256) k_krum_rows(const double* gram, int T, const int* inbox, int n,
+                                                             int groupsize, double* scores) {
+  krum_rows_body(PlainDot{gram, T}, inbox, n, groupsize, scores);
+}
+
+// the noise forms run beside the share MSMs, with the round waiting on them: high wave priority
 extern "C" __global__ void __launch_bounds__(256) k_krum_rows_noise(const double* gram, int T, int U1,
                                                                    const int* nz, const float* sc, int nn,
                                                                    const int* inbox, int n, int groupsize,
                                                                    double* scores) {
-  krum_rows_noise_body(gram, T, U1, NoisePtr{nz, sc}, nn, inbox, n, groupsize, scores);
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  krum_rows_body(NoiseDot<NoisePtr>{gram, T, U1, {nz, sc}, nn}, inbox, n, groupsize, scores);
 }
 
 extern "C" __global__ void __launch_bounds__(256) k_krum_rows_noise_ka(const double* gram, int T, int U1, NoiseArg q,
                                                                       int nn, const int* inbox, int n, int groupsize,
                                                                       double* scores) {
-  krum_rows_noise_body(gram, T, U1, NoiseByVal{&q}, nn, inbox, n, groupsize, scores);
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  krum_rows_body(NoiseDot<NoiseByVal>{gram, T, U1, {&q}, nn}, inbox, n, groupsize, scores);
 }
 
 // h_acc / h_node (nullable): the same verdicts written straight into pinned host memory (the host reads them
@@ -796,23 +783,21 @@ __device__ void bitonic_sort_lds(double* a, int npow2) {
 }
 }  // namespace
 
-template <bool NOISE>
-__global__ void __launch_bounds__(1024) k_krum_rows_big(const double* gram, int T, int U1, const int* nz,
-                                                        const float* sc, int nn, const int* inbox, int n, int npow2,
-                                                        int groupsize, double* scores) {
+template <class Dot>
+__global__ void __launch_bounds__(1024) k_krum_rows_big(Dot dot, const int* inbox, int n, int npow2, int groupsize,
+                                                        double* scores) {
   extern __shared__ double row[];   // [npow2]
   __shared__ double xaa;
   const int i = blockIdx.x, v = blockIdx.y;
   const int* box = inbox + (size_t)v * n;
   const int a = box[i];
-  if (threadIdx.x == 0) xaa = NOISE ? xx_dot(gram, T, U1, nz, sc, nn, a, a) : gram_at(gram, T, a, a);
+  if (threadIdx.x == 0) xaa = dot(a, a);
   __syncthreads();
   for (int t = threadIdx.x; t < npow2; t += blockDim.x) {
     double val = __builtin_huge_val();
     if (t < n) {
       const int b = box[t];
-      val = NOISE ? xaa + xx_dot(gram, T, U1, nz, sc, nn, b, b) - 2.0 * xx_dot(gram, T, U1, nz, sc, nn, a, b)
-                  : xaa + gram_at(gram, T, b, b) - 2.0 * gram_at(gram, T, a, b);
+      val = xaa + dot(b, b) - 2.0 * dot(a, b);
     }
     row[t] = val;
   }
@@ -870,7 +855,7 @@ int krum_vote_any(hipStream_t s, const double* scores, const int* inbox, int V, 
                        cap, acc, node, h_out, h_out != nullptr ? h_out + (size_t)V * n : nullptr, amap, nspec, alive);
   } else {
     if (ws == nullptr) return -1;
-    hipMemsetAsync(ws, 0, (size_t)U * sizeof(int), s);
+    if (hipMemsetAsync(ws, 0, (size_t)U * sizeof(int), s) != hipSuccess) return -1;
     hipLaunchKernelGGL(k_krum_select_big, dim3(V), dim3(1024), (size_t)n * sizeof(double), s, scores, inbox, n,
                        n_accept, acc, ws);
     hipLaunchKernelGGL(k_krum_cap_big, dim3((U + 255) / 256), dim3(256), 0, s, (const int*)ws, lead_rank, U, need, cap,
@@ -982,71 +967,114 @@ extern "C" int bsc_weighted_rows(const float* X, int n, int D, const double* w, 
 }
 
 // =====================================================================================
-// K2: classification error of a softmax model over up to two row sets in ONE launch (test rows
-// [0, split), attack rows [split, N)): err[row >= split] += #(argmax != label).
-// One wave per 16-row tile: logits = X_tile[16 x D_IN] . W^T on v_mfma_f32_16x16x4f32 (lane l
-// holds A[row l&15][k l>>4] with the (x-0.5)/0.5 transform fused and B[k][class l&15]; two
-// accumulators hide the 40-cycle dependent latency, loads are issued 8 k-steps ahead), then the
-// argmax across the 16 class lanes by xor-shuffles (first maximum, like np.argmax) and one atomic
-// per (wave, set).  Replaces a wave-per-row kernel that re-staged W into 64 KB of LDS per block.
+// K2: softmax scoring of 16-row tiles, shared by k_eval_error, k_eval_error_t and k_roni_counts.
+// One block per tile: logits = A_tile[16 x D_IN] . B^T on v_mfma_f32_16x16x4f32 (lane l holds
+// A[row l&15][k l>>4] and B[k l>>4][class l&15]).  The 4 waves split K; each runs 8 k-groups (of 4
+// features) per step on two accumulators (they hide the 40-cycle dependent latency; loads are issued 8
+// k-groups ahead), then a guarded one-group tail on the first accumulator; acc0 + acc1 goes to LDS and wave
+// 0 sums the four partials as (0 + 1) + (2 + 3), adds the bias and takes the argmax across the 16 class
+// lanes by xor-shuffles (first maximum, like np.argmax).  That order is part of the result: RONI's counts
+// equal the evaluation's exactly because both run this one body.
+//   A sources: EvalRows  -- row-major rows, (x - tsub) * tmul fused
+//              EvalTiles -- cached pre-transformed tiles, one coalesced 256-byte load per k-group
+//   B sources: ModelB      -- (float)W[e]
+//              ModelPlusB  -- (float)(W[e] + (double)U[c][e]): the sum in fp64, rounded once
+// A partial last k-group (D_IN % 4 != 0) is summed where each caller's stop puts it: the row kernels stop at
+// the end of the wave's features, so it goes through the tail, into acc0; the tile kernel stops at the end of its
+// (padded) k-groups, so it can sit in the unrolled loop and land in acc1.  The two orders differ in the last bits.
 // =====================================================================================
-extern "C" __global__ void __launch_bounds__(256) k_eval_error(const float* X, const int* y, int N, int D_IN,
-                                                              int D_OUT, const double* W, int transform, int split,
-                                                              unsigned int* err) {
-  // one block per 16-row tile; its 4 waves split K and reduce the logits through LDS
-  __shared__ float red[4][4][64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int row0 = blockIdx.x * 16;
-  const int i = lane & 15, kk = lane >> 4;
-  const float* xr = X + (size_t)min(row0 + i, N - 1) * D_IN;
-  const bool cval = i < D_OUT;
-  const double* wr = W + (size_t)(cval ? i : 0) * D_IN;
-  const float tsub = transform ? 0.5f : 0.f, tmul = transform ? 2.f : 1.f;
+namespace {
+// A sources: element (lane's row, feature k + kk) of the k-group at k (a multiple of 4)
+struct EvalRows {
+  static constexpr bool kPadded = false;
+  const float* xr;   // this lane's row
+  float tsub, tmul;
+  int klim;          // end of the wave's K range: nothing is read or summed from there on
+  __device__ __forceinline__ float load(int k, int kk) const { return xr[k + kk]; }
+  __device__ __forceinline__ float operand(float x) const { return (x - tsub) * tmul; }
+};
+struct EvalTiles {
+  static constexpr bool kPadded = true;   // whole k-groups, zeros past D_IN: loads need no guard
+  const float* xp;   // tile base + lane
+  int klim;          // D_IN: B is not read from there on
+  __device__ __forceinline__ float load(int k, int) const { return xp[(size_t)k * 16]; }
+  __device__ __forceinline__ float operand(float x) const { return x; }
+};
+// the B sources index from where they are pointed: the lane's class row for the logits, the model for the bias
+struct ModelB {
+  const double* w;
+  __device__ __forceinline__ float operator()(int k) const { return (float)w[k]; }
+};
+struct ModelPlusB {
+  const double* w;
+  const float* u;   // the candidate update, laid out like the model
+  bool upd;
+  __device__ __forceinline__ float operator()(int k) const { return upd ? (float)(w[k] + (double)u[k]) : (float)w[k]; }
+};
+
+// the tile's logits, as four per-wave partials in red: the wave's k-groups from k0 (a multiple of 4) up to kstop,
+// 8 per unrolled step while 32 features remain before kstop, then one at a time.  wb: the B source at this lane's
+// class row (cval: the lane has a class).  Returns true in wave 0, which goes on to score; the other waves are done.
+template <class A, class B>
+__device__ __forceinline__ bool softmax_tile_logits(float (&red)[4][4][64], const A& xa, const B& wb, bool cval,
+                                                    int k0, int kstop) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, kk = lane >> 4;
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const int kq = ((D_IN + 15) / 16) * 4;  // this wave's K range: multiple of 4
-  int k0 = wid * kq;
-  const int kend = min(D_IN, k0 + kq);
-  for (; k0 + 32 <= kend; k0 += 32) {
+  for (; k0 + 32 <= kstop; k0 += 32) {
     float a[8], b[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int k = k0 + 4 * u + kk;
-      a[u] = xr[k];
-      b[u] = cval ? (float)wr[k] : 0.f;
+      a[u] = xa.load(k0 + 4 * u, kk);
+      b[u] = (cval && (!A::kPadded || k < xa.klim)) ? wb(k) : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 8; u += 2) {
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32((a[u] - tsub) * tmul, b[u], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32((a[u + 1] - tsub) * tmul, b[u + 1], acc1, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.operand(a[u]), b[u], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.operand(a[u + 1]), b[u + 1], acc1, 0, 0, 0);
     }
   }
-  for (; k0 < kend; k0 += 4) {
+  for (; k0 < kstop; k0 += 4) {
     const int k = k0 + kk;
-    const float a = k < kend ? (xr[k] - tsub) * tmul : 0.f;
-    const float b = (k < kend && cval) ? (float)wr[k] : 0.f;
+    const bool in = k < xa.klim;
+    const float a = (A::kPadded || in) ? xa.operand(xa.load(k0, kk)) : 0.f;
+    const float b = (in && cval) ? wb(k) : 0.f;
     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc0, 0, 0, 0);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc0[r] + acc1[r];
   __syncthreads();
-  if (wid != 0) return;
-  const float bias = cval ? (float)W[(size_t)D_OUT * D_IN + i] : 0.f;
+  return wid == 0;
+}
+
+// wave 0: the predicted class of tile row (lane >> 4) * 4 + r (the D layout of 16x16x4 f32: lane l holds
+// D[row (l>>4)*4 + r][class l&15]), in every lane of the row's 16
+__device__ __forceinline__ int softmax_tile_class(const float (&red)[4][4][64], int r, bool cval, float bias) {
+  const int lane = threadIdx.x & 63;
+  const float logit = (red[0][r][lane] + red[1][r][lane]) + (red[2][r][lane] + red[3][r][lane]);
+  float bv = cval ? logit + bias : -__builtin_huge_valf();
+  int bc = lane & 15;
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 16);
+    const int oc = __shfl_xor(bc, o, 16);
+    if (ov > bv || (ov == bv && oc < bc)) {
+      bv = ov;
+      bc = oc;
+    }
+  }
+  return bc;
+}
+
+// the evaluation kernels' epilogue: misses over up to two row sets (rows [0, split) and [split, N)), one atomic
+// per (wave, set): err[row >= split] += #(argmax != label)
+__device__ __forceinline__ void eval_count_sets(const float (&red)[4][4][64], int row0, bool cval, float bias,
+                                                const int* y, int N, int split, unsigned int* err) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
   unsigned int cnt0 = 0, cnt1 = 0;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    // D layout of 16x16x4 f32: lane l holds D[row (l>>4)*4 + r][class l&15]
-    const float logit = (red[0][r][lane] + red[1][r][lane]) + (red[2][r][lane] + red[3][r][lane]);
-    float bv = cval ? logit + bias : -__builtin_huge_valf();
-    int bc = i;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 16);
-      const int oc = __shfl_xor(bc, o, 16);
-      if (ov > bv || (ov == bv && oc < bc)) {
-        bv = ov;
-        bc = oc;
-      }
-    }
+    const int bc = softmax_tile_class(red, r, cval, bias);
     const int row = row0 + kk * 4 + r;
     if (i == 0 && row < N && bc != y[row]) {
       if (row < split) ++cnt0;
@@ -1058,76 +1086,47 @@ extern "C" __global__ void __launch_bounds__(256) k_eval_error(const float* X, c
     if (cnt1) atomicAdd(err + 1, cnt1);
   }
 }
+}  // namespace
+
+// classification error of a softmax model over up to two row sets in ONE launch (test rows [0, split), attack
+// rows [split, N)), on row-major X with the (x - 0.5) / 0.5 transform fused
+extern "C" __global__ void __launch_bounds__(256) k_eval_error(const float* X, const int* y, int N, int D_IN,
+                                                              int D_OUT, const double* W, int transform, int split,
+                                                              unsigned int* err) {
+  __shared__ float red[4][4][64];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int row0 = blockIdx.x * 16;
+  const int i = lane & 15;
+  const bool cval = i < D_OUT;
+  const int kq = ((D_IN + 15) / 16) * 4;  // this wave's K range: multiple of 4
+  const int k0 = wid * kq, kend = min(D_IN, k0 + kq);
+  const EvalRows xa{X + (size_t)min(row0 + i, N - 1) * D_IN, transform ? 0.5f : 0.f, transform ? 2.f : 1.f, kend};
+  const ModelB wb{W + (size_t)(cval ? i : 0) * D_IN};
+  if (!softmax_tile_logits(red, xa, wb, cval, k0, kend)) return;
+  const float bias = cval ? ModelB{W}(D_OUT * D_IN + i) : 0.f;
+  eval_count_sets(red, row0, cval, bias, y, N, split, err);
+}
 
 // The same on a cached, pre-transformed test set: Xt[tile][g][64] holds (x - 0.5) / 0.5 of row
 // tile*16 + (l & 15), feature 4g + (l >> 4) for lane l -- exactly the A operand of one
-// v_mfma_f32_16x16x4f32 step -- built once per task (the test rows never change).  Each MFMA step is one
-// coalesced 256-byte load: the row-strided gathers and the per-element transform of k_eval_error are gone.
+// v_mfma_f32_16x16x4f32 step -- built once per task (the test rows never change): no row-strided gathers and
+// no per-element transform.  Ahead of the share MSM's waves (the evaluation is read one round later and
+// must be done by then under that load).
 extern "C" __global__ void __launch_bounds__(256) k_eval_error_t(const float* Xt, const int* y, int N, int KG, int D_IN,
                                                                 int D_OUT, const double* W, int split,
                                                                 unsigned int* err, unsigned int* err_host) {
   BSC_SET_PRIO(BSC_PRIO_AHEAD);
-  // 4 waves per tile split the K loop (latency: the evaluation is read one round later and must be done by
-  // then under the share MSM's load), then reduce the logits through LDS
   __shared__ float red[4][4][64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, tile = blockIdx.x;
-  const int i = lane & 15, kk = lane >> 4;
+  const int i = lane & 15;
   const bool cval = i < D_OUT;
-  const double* wr = W + (size_t)(cval ? i : 0) * D_IN;
-  const float* xp = Xt + (size_t)tile * KG * 64 + lane;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const int gq = (KG + 3) / 4;
-  int g = wid * gq;
-  const int gend = min(KG, g + gq);
-  for (; g + 8 <= gend; g += 8) {
-    float a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a[u] = xp[(size_t)(g + u) * 64];
-      const int k = 4 * (g + u) + kk;
-      b[u] = (cval && k < D_IN) ? (float)wr[k] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u += 2) {
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u + 1], b[u + 1], acc1, 0, 0, 0);
-    }
-  }
-  for (; g < gend; ++g) {
-    const int k = 4 * g + kk;
-    const float b = (cval && k < D_IN) ? (float)wr[k] : 0.f;
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xp[(size_t)g * 64], b, acc0, 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc0[r] + acc1[r];
-  __syncthreads();
-  if (wid != 0) return;
-  const float bias = cval ? (float)W[(size_t)D_OUT * D_IN + i] : 0.f;
-  unsigned int cnt0 = 0, cnt1 = 0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float logit = (red[0][r][lane] + red[1][r][lane]) + (red[2][r][lane] + red[3][r][lane]);
-    float bv = cval ? logit + bias : -__builtin_huge_valf();
-    int bc = i;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 16);
-      const int oc = __shfl_xor(bc, o, 16);
-      if (ov > bv || (ov == bv && oc < bc)) {
-        bv = ov;
-        bc = oc;
-      }
-    }
-    const int row = tile * 16 + kk * 4 + r;
-    if (i == 0 && row < N && bc != y[row]) {
-      if (row < split) ++cnt0;
-      else ++cnt1;
-    }
-  }
-  if (i == 0) {
-    if (cnt0) atomicAdd(err, cnt0);
-    if (cnt1) atomicAdd(err + 1, cnt1);
-  }
+  const int gq = (KG + 3) / 4;   // this wave's k-groups
+  const int g0 = wid * gq, gend = min(KG, g0 + gq);
+  const EvalTiles xa{Xt + (size_t)tile * KG * 64 + lane, D_IN};
+  const ModelB wb{W + (size_t)(cval ? i : 0) * D_IN};
+  if (!softmax_tile_logits(red, xa, wb, cval, 4 * g0, 4 * gend)) return;
+  const float bias = cval ? ModelB{W}(D_OUT * D_IN + i) : 0.f;
+  eval_count_sets(red, tile * 16, cval, bias, y, N, split, err);
   // err_host (bsc_eval_error_t_rb): k_eval_finish, the next launch, hands the counts to the host and re-zeroes
   // them.  (A last-tile hand-off inside this kernel needed an agent-scope fence per wave -- on gfx950 an L2
   // write-back + invalidate, ~625 of them beside the share MSMs.)
@@ -1150,12 +1149,11 @@ extern "C" __global__ void __launch_bounds__(64) k_eval_finish(unsigned int* err
 // Committee RONI (VerifyUpdateRONI, main.go:191-233): every local verifier's minibatch scored under the base
 // model and under W + U[c] for every row c of its inbox, in ONE launch.  counts[v][0] = #misclassified
 // minibatch rows of verifier v under W; counts[v][1 + j] the same under W + U[cand[v][j]].
-// One block per (column, verifier, 16-row tile of the minibatch).  The arithmetic is k_eval_error's, step for
-// step (K partition over the 4 waves, the two accumulators, the guarded tail, the LDS reduction order, the bias
-// add, the first-maximum argmax), with the B operand (float)(W[k] + (double)U[c][k]) formed in registers -- what
-// the host loop's `W + X[i].double()` followed by k_eval_error's (float)wr[k] gives -- so the logits, and with
-// them the counts, are bit-identical to one k_eval_error launch per (verifier, candidate).  The minibatch rows
-// are gathered by index (rows: absolute rows of X); slots past nrows[v] load a clamped row and are not counted.
+// One block per (column, verifier, 16-row tile of the minibatch), on K2's scoring body with k_eval_error's A
+// source and the B operand (float)(W[k] + (double)U[c][k]) formed in registers -- what the host loop's
+// `W + X[i].double()` followed by k_eval_error's (float)W[k] gives -- so the logits, and with them the counts,
+// are bit-identical to one k_eval_error launch per (verifier, candidate).  The minibatch rows are gathered by
+// index (rows: absolute rows of X); slots past nrows[v] load a clamped row and are not counted.
 // =====================================================================================
 extern "C" __global__ void __launch_bounds__(256) k_roni_counts(const float* X, const int* y, long long NX, int D_IN,
                                                                int D_OUT, const double* W, const float* U, int n_cand,
@@ -1170,64 +1168,23 @@ extern "C" __global__ void __launch_bounds__(256) k_roni_counts(const float* X, 
   const int i = lane & 15, kk = lane >> 4;
   const long long* rv = rows + (size_t)v * Bmax;
   const long long gr = min(max(rv[min(row0 + i, nr - 1)], 0ll), NX - 1);
-  const float* xr = X + (size_t)gr * D_IN;
   const bool cval = i < D_OUT;
-  const size_t wo = (size_t)(cval ? i : 0) * D_IN;
-  const double* wr = W + wo;
   // column 0 is the base model; an inbox slot without a row (cand < 0 or past U) is scored as the base model
   const int c = col > 0 ? cand[(size_t)v * ni + (col - 1)] : -1;
   const bool upd = c >= 0 && c < n_cand;
   const size_t D = (size_t)D_OUT * D_IN + D_OUT;
-  const float* uc = U + (upd ? (size_t)c * D : 0);
-  const float* ur = uc + wo;
-  const float tsub = transform ? 0.5f : 0.f, tmul = transform ? 2.f : 1.f;
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   const int kq = ((D_IN + 15) / 16) * 4;  // this wave's K range: multiple of 4
-  int k0 = wid * kq;
-  const int kend = min(D_IN, k0 + kq);
-  for (; k0 + 32 <= kend; k0 += 32) {
-    float a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = k0 + 4 * u + kk;
-      a[u] = xr[k];
-      b[u] = cval ? (upd ? (float)(wr[k] + (double)ur[k]) : (float)wr[k]) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u += 2) {
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32((a[u] - tsub) * tmul, b[u], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32((a[u + 1] - tsub) * tmul, b[u + 1], acc1, 0, 0, 0);
-    }
-  }
-  for (; k0 < kend; k0 += 4) {
-    const int k = k0 + kk;
-    const bool in = k < kend;
-    const float a = in ? (xr[k] - tsub) * tmul : 0.f;
-    const float b = (in && cval) ? (upd ? (float)(wr[k] + (double)ur[k]) : (float)wr[k]) : 0.f;
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc0, 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc0[r] + acc1[r];
-  __syncthreads();
-  if (wid != 0) return;
-  const size_t bo = (size_t)D_OUT * D_IN + (cval ? i : 0);
-  const float bias = cval ? (upd ? (float)(W[bo] + (double)uc[bo]) : (float)W[bo]) : 0.f;
+  const int k0 = wid * kq, kend = min(D_IN, k0 + kq);
+  const EvalRows xa{X + (size_t)gr * D_IN, transform ? 0.5f : 0.f, transform ? 2.f : 1.f, kend};
+  const float* uc = U + (upd ? (size_t)c * D : 0);
+  const size_t wo = (size_t)(cval ? i : 0) * D_IN;
+  const ModelPlusB wb{W + wo, uc + wo, upd};
+  if (!softmax_tile_logits(red, xa, wb, cval, k0, kend)) return;
+  const float bias = cval ? ModelPlusB{W, uc, upd}(D_OUT * D_IN + i) : 0.f;
   unsigned int cnt = 0;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    // D layout of 16x16x4 f32: lane l holds D[row (l>>4)*4 + r][class l&15]
-    const float logit = (red[0][r][lane] + red[1][r][lane]) + (red[2][r][lane] + red[3][r][lane]);
-    float bv = cval ? logit + bias : -__builtin_huge_valf();
-    int bc = i;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 16);
-      const int oc = __shfl_xor(bc, o, 16);
-      if (ov > bv || (ov == bv && oc < bc)) {
-        bv = ov;
-        bc = oc;
-      }
-    }
+    const int bc = softmax_tile_class(red, r, cval, bias);
     const int row = row0 + kk * 4 + r;
     if (i == 0 && row < nr && bc != y[min(max(rv[row], 0ll), NX - 1)]) ++cnt;
   }
@@ -1573,8 +1530,8 @@ extern "C" int bsc_krum_committee(const float* X, int U, int D, int kchunk, cons
     hipLaunchKernelGGL(k_krum_rows, dim3(n, V), dim3(256), 0, s, gram, T, inbox, n, groupsize, scores);
   } else {
     const int np2 = pow2_at_least(n);
-    hipLaunchKernelGGL(k_krum_rows_big<false>, dim3(n, V), dim3(1024), (size_t)np2 * sizeof(double), s, gram, T, U,
-                       (const int*)nullptr, (const float*)nullptr, 0, inbox, n, np2, groupsize, scores);
+    hipLaunchKernelGGL(k_krum_rows_big<PlainDot>, dim3(n, V), dim3(1024), (size_t)np2 * sizeof(double), s,
+                       PlainDot{gram, T}, inbox, n, np2, groupsize, scores);
   }
   if (krum_vote_any(s, scores, inbox, V, n, n_accept, U, need, lead_rank, cap, acc, node, ws) != 0) return -1;
   return (int)hipGetLastError();
@@ -1605,6 +1562,41 @@ extern "C" int bsc_gram_stacked(const float* X, int U1, const float* X2, int U2,
                                 double* part, double* gram, unsigned int* count, const double* nn, void* stream) {
   return bsc_gram_stacked_range(X, U1, X2, U2, stride2, D, kchunk, 0, 0, part, gram, count, nn, stream);
 }
+namespace {
+// the noise-aware committee Krum on a finished stacked Gram: rows kernel, then the vote.  nz / sc [U1][nn] are
+// device arrays, or (host_tabs) host arrays that travel in the rows kernel's argument block -- which holds
+// U1 * nn <= NOISE_ARG_MAX entries and exists for n <= 256 only; else -2
+int krum_committee_noise_any(const double* gram, int U1, int U, const int* nz, const float* sc, bool host_tabs,
+                             int nn, const int* inbox, int V, int n, int groupsize, int n_accept, int need,
+                             const int* lead_rank, int cap, double* scores, int* acc, int* node, int* ws, int* h_out,
+                             const int* amap, int nspec, int* alive, void* stream) {
+  if (U1 <= 0 || V <= 0 || n <= 0) return 0;
+  if (U > 8192 || U1 > 8192 || n > 4096 || V > 64 || n > U1 || nn <= 0 || nn > 16) return -1;
+  if (host_tabs && ((long long)U1 * nn > NOISE_ARG_MAX || n > 256)) return -2;
+  const int T = (U + 15) / 16;
+  hipStream_t s = (hipStream_t)stream;
+  if (host_tabs) {
+    NoiseArg q;
+    for (int i = 0; i < U1 * nn; ++i) {
+      q.nz[i] = nz[i];
+      q.sc[i] = sc[i];
+    }
+    hipLaunchKernelGGL(k_krum_rows_noise_ka, dim3(n, V), dim3(256), 0, s, gram, T, U1, q, nn, inbox, n, groupsize,
+                       scores);
+  } else if (n <= 256) {
+    hipLaunchKernelGGL(k_krum_rows_noise, dim3(n, V), dim3(256), 0, s, gram, T, U1, nz, sc, nn, inbox, n, groupsize,
+                       scores);
+  } else {
+    const int np2 = pow2_at_least(n);
+    hipLaunchKernelGGL(k_krum_rows_big<NoiseDot<NoisePtr>>, dim3(n, V), dim3(1024), (size_t)np2 * sizeof(double), s,
+                       NoiseDot<NoisePtr>{gram, T, U1, {nz, sc}, nn}, inbox, n, np2, groupsize, scores);
+  }
+  if (krum_vote_any(s, scores, inbox, V, n, n_accept, U1, need, lead_rank, cap, acc, node, ws, h_out, amap, nspec,
+                    alive) != 0)
+    return -1;
+  return (int)hipGetLastError();
+}
+}  // namespace
 // h_out (nullable): [V * n + U1] pinned host mirror of (acc, node), written by the vote itself (acc and node
 // must be contiguous there too); amap / nspec / alive (nullable): the speculative MSM's row flags set in the
 // same kernel
@@ -1612,64 +1604,17 @@ extern "C" int bsc_krum_committee_noise2(const double* gram, int U1, int U, cons
                                          const int* inbox, int V, int n, int groupsize, int n_accept, int need,
                                          const int* lead_rank, int cap, double* scores, int* acc, int* node, int* ws,
                                          int* h_out, const int* amap, int nspec, int* alive, void* stream) {
-  if (U1 <= 0 || V <= 0 || n <= 0) return 0;
-  if (U > 8192 || U1 > 8192 || n > 4096 || V > 64 || n > U1 || nn <= 0 || nn > 16) return -1;
-  const int T = (U + 15) / 16;
-  hipStream_t s = (hipStream_t)stream;
-  if (n <= 256) {
-    hipLaunchKernelGGL(k_krum_rows_noise, dim3(n, V), dim3(256), 0, s, gram, T, U1, nz, sc, nn, inbox, n, groupsize,
-                       scores);
-  } else {
-    const int np2 = pow2_at_least(n);
-    hipLaunchKernelGGL(k_krum_rows_big<true>, dim3(n, V), dim3(1024), (size_t)np2 * sizeof(double), s, gram, T, U1,
-                       nz, sc, nn, inbox, n, np2, groupsize, scores);
-  }
-  if (krum_vote_any(s, scores, inbox, V, n, n_accept, U1, need, lead_rank, cap, acc, node, ws, h_out, amap, nspec,
-                    alive) != 0)
-    return -1;
-  return (int)hipGetLastError();
+  return krum_committee_noise_any(gram, U1, U, nz, sc, false, nn, inbox, V, n, groupsize, n_accept, need, lead_rank,
+                                  cap, scores, acc, node, ws, h_out, amap, nspec, alive, stream);
 }
-// the same with the noisers' ids / weights read from HOST memory (nz_host / sc_host [U1][nn]) into the rows
-// kernel's argument block (U1 * nn <= NOISE_ARG_MAX, n <= 256; else -2: the caller uploads and uses the above)
+// the same with the noisers' ids / weights read from HOST memory (nz_host / sc_host [U1][nn]); -2: the caller
+// uploads them and uses the above
 extern "C" int bsc_krum_committee_noise_ka(const double* gram, int U1, int U, const int* nz_host, const float* sc_host,
                                            int nn, const int* inbox, int V, int n, int groupsize, int n_accept,
                                            int need, const int* lead_rank, int cap, double* scores, int* acc, int* node,
                                            int* ws, int* h_out, const int* amap, int nspec, int* alive, void* stream) {
-  if (U1 <= 0 || V <= 0 || n <= 0) return 0;
-  if (U > 8192 || U1 > 8192 || n > 4096 || V > 64 || n > U1 || nn <= 0 || nn > 16) return -1;
-  if ((long long)U1 * nn > NOISE_ARG_MAX || n > 256) return -2;
-  NoiseArg q;
-  for (int i = 0; i < U1 * nn; ++i) {
-    q.nz[i] = nz_host[i];
-    q.sc[i] = sc_host[i];
-  }
-  const int T = (U + 15) / 16;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_krum_rows_noise_ka, dim3(n, V), dim3(256), 0, s, gram, T, U1, q, nn, inbox, n, groupsize,
-                     scores);
-  if (krum_vote_any(s, scores, inbox, V, n, n_accept, U1, need, lead_rank, cap, acc, node, ws, h_out, amap, nspec,
-                    alive) != 0)
-    return -1;
-  return (int)hipGetLastError();
-}
-extern "C" int bsc_krum_committee_noise(const double* gram, int U1, int U, const int* nz, const float* sc, int nn,
-                                        const int* inbox, int V, int n, int groupsize, int n_accept, int need,
-                                        const int* lead_rank, int cap, double* scores, int* acc, int* node, int* ws,
-                                        void* stream) {
-  if (U1 <= 0 || V <= 0 || n <= 0) return 0;
-  if (U > 8192 || U1 > 8192 || n > 4096 || V > 64 || n > U1 || nn <= 0 || nn > 16) return -1;
-  const int T = (U + 15) / 16;
-  hipStream_t s = (hipStream_t)stream;
-  if (n <= 256) {
-    hipLaunchKernelGGL(k_krum_rows_noise, dim3(n, V), dim3(256), 0, s, gram, T, U1, nz, sc, nn, inbox, n, groupsize,
-                       scores);
-  } else {
-    const int np2 = pow2_at_least(n);
-    hipLaunchKernelGGL(k_krum_rows_big<true>, dim3(n, V), dim3(1024), (size_t)np2 * sizeof(double), s, gram, T, U1,
-                       nz, sc, nn, inbox, n, np2, groupsize, scores);
-  }
-  if (krum_vote_any(s, scores, inbox, V, n, n_accept, U1, need, lead_rank, cap, acc, node, ws) != 0) return -1;
-  return (int)hipGetLastError();
+  return krum_committee_noise_any(gram, U1, U, nz_host, sc_host, true, nn, inbox, V, n, groupsize, n_accept, need,
+                                  lead_rank, cap, scores, acc, node, ws, h_out, amap, nspec, alive, stream);
 }
 extern "C" int bsc_eval_error(const float* X, const int* y, int N, int D_IN, int D_OUT, const double* W,
                               int transform, int split, unsigned int* err, void* stream) {

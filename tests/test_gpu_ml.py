@@ -381,6 +381,23 @@ def test_krum_committee_matches_reference(U, n, V):
         assert not acc[v][torch.isin(rows, bad)].any()
 
 
+def test_krum_committee_smallest_group():
+    """One verifier, an inbox of 3 rows and groupsize 3: the kept range 1 <= rank < groupsize - 1 holds exactly
+    one rank (each row's score is its nearest neighbour's distance); 17 candidate rows span two Gram tiles and
+    the inbox takes rows of both."""
+    g = torch.Generator().manual_seed(17)
+    X = torch.randn((17, 7850), generator=g) * 0.1
+    X[16] += 0.5                                                  # the far row: not accepted
+    inbox = torch.tensor([[3, 15, 16]], dtype=torch.int32)
+    rank = torch.randperm(17, generator=g).int()
+    acc_ref, node_ref = K.krum_committee_async(X, inbox, 3, 2, 1, rank, 0)()
+    acc, node = K.krum_committee_async(X.cuda(), inbox.cuda(), 3, 2, 1, rank.cuda(), 0)()
+    assert acc_ref.tolist() == [[True, True, False]]
+    assert torch.equal(acc, acc_ref)
+    assert torch.equal(node, node_ref)
+    assert torch.nonzero(node).flatten().tolist() == [3, 15]
+
+
 @pytest.mark.parametrize("U1,N,nn", [(94, 100, 2), (60, 64, 3)])
 def test_krum_committee_noise_aware_matches_explicit(U1, N, nn):
     """Phase-1 Gram over [deltas; noise vectors] + phase-2 assembly gives the same committee decisions as
@@ -467,11 +484,12 @@ def test_noise_table_fused_row_gather():
     assert torch.equal(got, full[rows.long()])
 
 
-@pytest.mark.parametrize("U,n,V", [(500, 400, 3), (1300, 700, 4)])
+@pytest.mark.parametrize("U,n,V", [(260, 257, 2), (500, 400, 3), (1300, 700, 4)])
 def test_krum_committee_large_inboxes(U, n, V):
     """Committees past the LDS fast path (inbox > 256 updates, > 1024 candidate rows; the reference's Krum
     has no size limit, client_obj.py:114-143): rows sorted in LDS + workspace vote, against the fp64
-    reference (BLAS Gram here: the test's rows have no near-ties)."""
+    reference (BLAS Gram here: the test's rows have no near-ties).  An inbox of 257 is the first on this path:
+    512 sorted slots, 255 of them padding."""
     g = torch.Generator().manual_seed(U + n)
     X = torch.randn((U, 7850), generator=g) * 0.1
     bad = torch.randperm(U, generator=g)[: U // 5]
@@ -544,6 +562,39 @@ def test_eval_errors_cached_tiles_repeated_launches():
         ra = K.eval_error(X[:split], y[:split], Wk, 784, 10)
         rb = K.eval_error(X[split:], y[split:], Wk, 784, 10)
         assert abs(a - ra) <= 1.0 / split and abs(b - rb) <= 1.0 / (1000 - split)
+
+
+@pytest.mark.parametrize("d_in,d_out", [(22, 3), (8742, 2)])
+def test_eval_error_kernels_at_other_k_shapes(d_in, d_out):
+    """k_eval_error and k_eval_error_t away from D_IN = 784, 37 rows (a ragged last tile) split 20 / 17.
+    d_in 22: the waves' K ranges are [0, 8), [8, 16), [16, 22) and empty -- a partial last k-group, an idle wave,
+    fewer than 16 classes; d_in 8742 (LFW): D_IN % 4 == 2, where the row kernel sums the partial k-group in its
+    tail and the tile kernel inside its unrolled loop.  Inputs as test_gpu_roni._case draws them (X uniform
+    [0, 1), W standard normal fp64), seed 0; expected: fp64 predictions on the host, leaving out rows whose fp64
+    top-two logit gap is below 1e-3 * max|logit| (fp32 may order those either way) -- at most 1 of the 37 may be
+    left out; seed 0 leaves out none at either shape (smallest relative gap 0.041 and 0.10).  Both kernels score
+    the kept rows, and the counts per set match exactly."""
+    N, split = 37, 20
+    g = torch.Generator().manual_seed(0)
+    X = torch.rand((N, d_in), generator=g, dtype=torch.float32)
+    y = torch.randint(0, d_out, (N,), generator=g, dtype=torch.int32)
+    W = torch.randn((d_out * d_in + d_out,), generator=g, dtype=torch.float64)
+    logits = ((X.double() - 0.5) * 2.0) @ W[: d_out * d_in].view(d_out, d_in).T + W[d_out * d_in:]
+    top = torch.topk(logits, 2, dim=1).values
+    keep = (top[:, 0] - top[:, 1]) >= 1e-3 * logits.abs().max(dim=1).values
+    assert int((~keep).sum()) <= 1
+    wrong = (logits.argmax(1) != y.long()) & keep
+    want = (int(wrong[:split].sum()), int(wrong[split:].sum()))
+    na, nb = int(keep[:split].sum()), int(keep[split:].sum())
+    Xc, yc, Wc = X[keep].cuda().contiguous(), y[keep].cuda().contiguous(), W.cuda()
+    a, b = K.eval_errors_async(Xc, yc, na, Wc, d_in, d_out)()
+    rows = (round(a * na), round(b * nb))
+    Xt = K.eval_tiles(Xc, transform=True)
+    assert tuple(Xt.shape) == ((na + nb + 15) // 16, (d_in + 3) // 4, 64)
+    a, b = K.eval_errors_async(Xc, yc, na, Wc, d_in, d_out, Xt=Xt)()
+    tiles = (round(a * na), round(b * nb))
+    print(d_in, "left out", N - na - nb, "fp64", want, "k_eval_error", rows, "k_eval_error_t", tiles)
+    assert rows == want and tiles == want
 
 
 @pytest.mark.parametrize("U1", [16, 23, 100])

@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.h"
+
 #define VG_MAX_SLOTS 128   // local peer slots per rank
 #define VG_MAX_NZ 256      // maxlocal x nn noiser entries per rank
 #define VG_MAX_WORKERS 1024 // workers whose commitment rows are read back (weak scaling: 800 peers)

@@ -15,6 +15,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "launchers.h"
 #define BSC_PRIO_FLAG bsc_prio_on_ml
 #include "wave_prio.h"
 BSC_PRIO_SETTER(bsc_wave_prio_ml)
@@ -845,7 +846,6 @@ extern "C" __global__ void __launch_bounds__(256) k_krum_cap_big(const int* sigs
   node[w] = keep;
 }
 
-extern "C" int bsc_set_alive(const int* accept, const int* src, int n, int* alive, void* stream);
 namespace {
 int krum_vote_any(hipStream_t s, const double* scores, const int* inbox, int V, int n, int n_accept, int U, int need,
                   const int* lead_rank, int cap, int* acc, int* node, int* ws, int* h_out = nullptr,
@@ -1716,21 +1716,14 @@ extern "C" int bsc_recover_w_clock(const long long* ys, int nrows, long long rst
   return (int)hipGetLastError();
 }
 
-extern "C" int bsc_recover_w_strided(const long long* ys, int nrows, long long rstride, int nch, int T, const int* mask,
-                                     const int* ycols, const int* xs, int npts, const long long* A, const int* basis,
-                                     int poly, int shift, unsigned long long inv_lo, unsigned long long inv_hi, int d,
-                                     const double* W, double qscale, double* W_new, long long* coeffs, int* status,
-                                     long long* agg_out, double* h_W, int* h_status, void* stream) {
-  return bsc_recover_w_clock(ys, nrows, rstride, nch, T, mask, ycols, xs, npts, A, basis, poly, shift, inv_lo, inv_hi, d,
-                             W, qscale, W_new, coeffs, status, agg_out, h_W, h_status, nullptr, stream);
-}
-
+// a dense [nrows][nch][T] tensor, no host mirrors
 extern "C" int bsc_recover_w(const long long* ys, int nrows, int nch, int T, const int* mask, const int* ycols,
                              const int* xs, int npts, const long long* A, const int* basis, int poly, int shift,
                              unsigned long long inv_lo, unsigned long long inv_hi, int d, const double* W, double qscale,
                              double* W_new, long long* coeffs, int* status, long long* agg_out, void* stream) {
-  return bsc_recover_w_strided(ys, nrows, (long long)nch * T, nch, T, mask, ycols, xs, npts, A, basis, poly, shift,
-                               inv_lo, inv_hi, d, W, qscale, W_new, coeffs, status, agg_out, nullptr, nullptr, stream);
+  return bsc_recover_w_clock(ys, nrows, (long long)nch * T, nch, T, mask, ycols, xs, npts, A, basis, poly, shift,
+                             inv_lo, inv_hi, d, W, qscale, W_new, coeffs, status, agg_out, nullptr, nullptr, nullptr,
+                             stream);
 }
 
 extern "C" int bsc_add_rows(const float* delta, int D, const int* rows, int nrows, const double* W, double* W_new,

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "bn256_dev.h"
+#include "launchers.h"
 #define BSC_PRIO_FLAG bsc_prio_on_msm
 #include "wave_prio.h"
 BSC_PRIO_SETTER(bsc_wave_prio_msm)
@@ -192,8 +193,7 @@ extern "C" __global__ void __launch_bounds__(64) k_fb_table(const uint32_t* base
 // group is T lanes instead of T+1 and no wave runs the commitment lane's extra c_0 addition.
 // out_y: int64 [nrows][nchunks][T].
 // The row list comes from device memory (rows) or from the kernel's argument block (RowArg, <= ROWARG_MAX
-// rows): the speculative MSM is launched the moment its rows are known, with no upload in front of it.
-#define ROWARG_MAX 248
+// rows, launchers.h): the speculative MSM is launched the moment its rows are known, with no upload in front of it.
 struct RowArg {
   int r[ROWARG_MAX];
 };

@@ -1,21 +1,24 @@
-// Native round driver pieces: the secure aggregation a round queues behind the committee's selection,
-// enqueued from C++ in ONE call instead of ~25 Python-level tensor / stream operations (each 5-20 us
-// of the round's host thread, which is the round's critical path).
+// Native round driver: what a round queues behind the committee's selection, enqueued from C++ in ONE call per
+// phase instead of ~25 Python-level tensor / stream operations (each 5-60 us of the round's host thread, which
+// is the round's critical path).  Every buffer is resident: registered once per run in the RoundCtx
+// (bsc_round_create, bsc_round_bind_outputs / _task / _multi, bsc_round_add_layout / _pre_slot,
+// bsc_round_set_spec_ring), so a call takes a handful of arguments and allocates nothing.  The launchers of
+// the individual kernels (msm.hip, ml.hip, gather.hip; launchers.h) are called directly.
 //
-// bsc_round_secagg  -- the miners' sums and the leader's recovery (aggregateSecret + recoverSecret,
-//                      DistSys/kyber.go:244-287,809-857) for the rows the selection kept:
-//                        side: chunk-commitment sums of the kept rows (the audit's input)
-//                        wit:  witness sums (no consumer on the protocol path; own low-priority stream)
-//                        main: fused share sums + exact recovery + W update (k_recover_w), then the
-//                              read-back of (status, W_new) into pinned memory, event `readback`
-// bsc_round_audit   -- verifyCommitment on the aggregate (kyber.go:564-577): main waits for the side
-//                      stream's sums, k_chunk_check, read-back of the verdicts, event `audit`
-// bsc_round_wait    -- host wait for one of the two events
-// bsc_round_partials / bsc_round_combine -- the same aggregation on several ranks, split around the one
-//                      all_gather the caller issues between them (below)
-//
-// The launchers of the individual kernels (msm.hip, ml.hip) are called directly; every buffer is
-// resident (allocated once by the engine), so the call allocates nothing.
+// Per round, one rank:
+//   bsc_round_spec_msm2 / _topup   the next round's speculative share MSM into its ring slot
+//   bsc_round_after_select         the selection's flags, the early audit sums, the miners' sums + the leader's
+//                                  recovery (aggregateSecret + recoverSecret, DistSys/kyber.go:244-287,809-857)
+//                                  with the read-back of (status, W_new), the next pre-step, the audit
+//   bsc_round_prestep_slot         the next round's pre-step alone (local step, commitments, Krum Gram)
+//   bsc_round_audit                verifyCommitment on the aggregate (kyber.go:564-577) alone
+//   bsc_round_wait                 host wait for the recovery's or an audit's read-back
+// Several ranks (one per GPU):
+//   bsc_round_select_partials / bsc_round_after_gather   the same aggregation split around the one all_gather
+//                                  the caller issues between them
+//   bsc_round_agg_multi            the same with the round's own RCCL communicator, collectives included
+//   bsc_round_vg_exchange          the verification row: pack, all_gather in place, unpack
+// The inner steps (csum_early, secagg, partials, combine, pick_W) are file-local and read the RoundCtx.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: the entry points are resolved at run time (bsc_rccl_load)
@@ -26,60 +29,7 @@
 #include <chrono>
 #include <thread>
 
-extern "C" int bsc_sum_rows2(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols,
-                             int ncols, const int* row_mask, uint32_t* out, void* stream);
-extern "C" int bsc_recover_w(const long long* ys, int nrows, int nch, int T, const int* mask, const int* ycols,
-                             const int* xs, int npts, const long long* A, const int* basis, int poly, int shift,
-                             unsigned long long inv_lo, unsigned long long inv_hi, int d, const double* W,
-                             double qscale, double* W_new, long long* coeffs, int* status, long long* agg_out,
-                             void* stream);
-extern "C" int bsc_recover_w_strided(const long long* ys, int nrows, long long rstride, int nch, int T, const int* mask,
-                                     const int* ycols, const int* xs, int npts, const long long* A, const int* basis,
-                                     int poly, int shift, unsigned long long inv_lo, unsigned long long inv_hi, int d,
-                                     const double* W, double qscale, double* W_new, long long* coeffs, int* status,
-                                     long long* agg_out, double* h_W, int* h_status, void* stream);
-extern "C" int bsc_recover_w_clock(const long long* ys, int nrows, long long rstride, int nch, int T, const int* mask,
-                                   const int* ycols, const int* xs, int npts, const long long* A, const int* basis,
-                                   int poly, int shift, unsigned long long inv_lo, unsigned long long inv_hi, int d,
-                                   const double* W, double qscale, double* W_new, long long* coeffs, int* status,
-                                   long long* agg_out, double* h_W, int* h_status, long long* h_clock, void* stream);
-extern "C" int bsc_segment_sum_h(const uint32_t* pts, int ngroups, int n, int stride, int off, uint32_t* out,
-                                 uint32_t* hout, void* stream);
-extern "C" int bsc_chunk_check_h(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
-                                 const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream);
-extern "C" int bsc_sum_rows_i64(const long long* ys, int R, long long C, const int* rows, int nsel, const int* mask,
-                                long long* out, void* stream);
-extern "C" int bsc_sum_rows_i64_tail(const long long* ys, int R, long long C, const int* mask, long long* out,
-                                     long long tail, void* stream);
-extern "C" int bsc_sum_cols_serial(const uint32_t* pts, int ncols_in, int nrows, const int* cols, int ncols,
-                                   const int* row_mask, uint32_t* out, void* stream);
-extern "C" int bsc_sum_rows2_pos(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols,
-                                 int ncols, const int* row_mask, uint32_t* out, void* stream);
-extern "C" int bsc_shares_msm(const long long* coeffs, int d, const int* rows, int nrows, const uint32_t* tbl_pk,
-                              const uint32_t* tbl_wb, int poly, int T, int B0, int NW, int commit_only,
-                              const int* alive, const int* compact, int group_rows, uint32_t* out_pts,
-                              long long* out_y, void* stream);
-extern "C" int bsc_softmax_step_ones(const float* X, const int* y, const long long* off, const int* ntrain,
-                                     const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
-                                     unsigned long long seed, int iteration, float max_norm, double qscale, float* delta,
-                                     long long* qdelta, float* loss, int lo, int* ones, int nones, void* stream);
-extern "C" int bsc_shares_msm_ka(const long long* coeffs, int d, const int* rows_host, int nrows, const uint32_t* tbl_pk,
-                                 const uint32_t* tbl_wb, int poly, int T, int B0, int NW, int commit_only,
-                                 const int* alive, int group_rows, uint32_t* out_pts, long long* out_y, void* stream);
-#define ROWARG_MAX 248   // msm.hip: rows passed in the MSM kernel's arguments
-extern "C" int bsc_gram_stacked(const float* X, int U1, const float* X2, int U2, long long stride2, int D, int kchunk,
-                                double* part, double* gram, unsigned int* count, const double* nn, void* stream);
-extern "C" int bsc_segment_sum(const uint32_t* pts, int ngroups, int n, int stride, int off, uint32_t* out,
-                               void* stream);
-extern "C" int bsc_gram_stacked_range(const float* X, int U1, const float* X2, int U2, long long stride2, int D,
-                                      int kchunk, int p0, int p1, double* part, double* gram, unsigned int* count,
-                                      const double* nn, void* stream);
-extern "C" int bsc_commit_rows(const long long* coeffs, int d, const int* rows, int nrows, const uint32_t* tbl_pk,
-                               int B0, int NW, uint32_t* partial, uint32_t* out, void* stream);
-extern "C" int bsc_chunk_check(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
-                               const uint32_t* csum, int nm, int nch, int* ok, void* stream);
-
-extern "C" int bsc_set_alive(const int* accept, const int* src, int n, int* alive, void* stream);
+#include "launchers.h"
 
 namespace {
 // resident state of the fused round calls (bsc_round_bind_* / bsc_round_add_*, registered once per run)
@@ -222,9 +172,6 @@ extern "C" int bsc_round_set_witness_stream(void* ctx, void* stream) {
   return 0;
 }
 
-extern "C" int bsc_wave_prio_ml(int on);
-extern "C" int bsc_wave_prio_msm(int on);
-extern "C" int bsc_wave_prio_vrf(int on);
 // the round kernels' wave priority classes (kernels/wave_prio.h) on or off, in every kernel file
 extern "C" int bsc_wave_prio(int on) {
   RC_CHECK(bsc_wave_prio_ml(on));
@@ -262,38 +209,38 @@ extern "C" void bsc_round_destroy(void* ctx) {
   delete c;
 }
 
+namespace {
+// One rank: the miners' sums and the leader's recovery for the R > 0 rows the selection kept.
+//   side: chunk-commitment sums of the kept rows (the audit's input; audit = 1 only)
+//   wit:  witness sums (no consumer on the protocol path; own low-priority stream)
+//   main: fused share sums + exact recovery + W update (k_recover_w), which writes (status, W_new) into the
+//         pinned read-back buffers itself -- event `readback`
 // pts [R][nch * (T + 1)][24] Jacobian shares + chunk commitments of the speculative rows, ys [R][nch][T]
-// share values, mask [R] the selection's keep flags; ccols [nch] / wcols [nwc] the commitment and witness
-// columns, ycols / xs [npts] the contributing miners' share columns and x-points; A / basis / shift /
-// inv the exact recovery weights of this miner layout; W the current model.  Outputs (resident):
-// W_new [d], coeffs [nch][poly], status [nch], agg [nch][npts], cs [nch][24], ws [nwc][24]; pinned host
-// copies h_status [nch], h_W [d].  audit = 0: no commitment sums.
-extern "C" int bsc_round_secagg(void* ctx, const uint32_t* pts, int R, const long long* ys, const int* mask,
-                                const int* ccols, const int* wcols, int nwc, const int* ycols, const int* xs, int npts,
-                                const long long* A, const int* basis, int shift, unsigned long long inv_lo,
-                                unsigned long long inv_hi, const double* W, double* W_new, long long* coeffs,
-                                int* status, long long* agg, uint32_t* cs, uint32_t* ws, int* h_status, double* h_W,
-                                int audit) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || R <= 0) return -1;
+// share values, mask [R] the selection's keep flags; L: the commitment / witness / share columns, x-points
+// and exact recovery weights of this miner layout, its resident agg [nch][npts] and ws [nwc][24]; W the current
+// model.  Further outputs (bound): W_new [d], coeffs [nch][poly], status [nch], cs [nch][24]; pinned h_status
+// [nch], h_W [d].  audit = 0: no commitment sums; audit = 2: they were queued early (csum_early).
+int secagg(RoundCtx* c, const Layout& L, const uint32_t* pts, int R, const long long* ys, const int* mask,
+           const double* W, double* W_new, int audit) {
   const int ncols_in = c->nch * (c->T + 1);
   RC_CHECK(hipEventRecord(c->ev_main, c->main));
-  if (audit == 1) {   // audit == 2: the commitment sums were queued early (bsc_round_csum_early)
+  if (audit == 1) {
     RC_CHECK(hipStreamWaitEvent(c->side, c->ev_main, 0));
-    RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, ccols, c->nch, mask, cs, c->side));
+    RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, L.ccols, c->nch, mask, c->cs, c->side));
     RC_CHECK(hipEventRecord(c->ev_side, c->side));
   }
   RC_CHECK(hipStreamWaitEvent(c->wit, c->ev_main, 0));
-  RC_CHECK(bsc_sum_cols_serial(pts, ncols_in, R, wcols, nwc, mask, ws, c->wit));
+  RC_CHECK(bsc_sum_cols_serial(pts, ncols_in, R, L.wcols, L.nwc, mask, L.ws, c->wit));
   RC_CHECK(spec_mark_read(c, mask));
-  // the recovery writes (status, W_new) into the pinned read-back buffers itself: no copies behind it
-  RC_CHECK(bsc_recover_w_strided(ys, R, (long long)c->nch * c->T, c->nch, c->T, mask, ycols, xs, npts, A, basis,
-                                 c->poly, shift, inv_lo, inv_hi, c->d, W, c->qscale, W_new, coeffs, status, agg, h_W,
-                                 h_status, c->main));
+  RC_CHECK(bsc_recover_w_clock(ys, R, (long long)c->nch * c->T, c->nch, c->T, mask, L.ycols, L.xs, L.npts, L.A,
+                               L.basis, c->poly, L.shift, L.inv_lo, L.inv_hi, c->d, W, c->qscale, W_new, c->coeffs,
+                               c->status, L.agg, c->h_W, c->h_status, nullptr, c->main));
   RC_CHECK(hipEventRecord(c->ev_readback, c->main));
   return 0;
 }
+}  // namespace
 
+// verifyCommitment on the aggregate: main waits for the commitment sums (ev_side), k_chunk_check, event `audit`.
 // h_ok: [2][nch] pinned; this audit's verdicts go to row aud_k (flipped per audit, bsc_round_audit_slot)
 extern "C" int bsc_round_audit(void* ctx, const long long* coeffs, const uint32_t* cs, int* ok, int* h_ok) {
   RoundCtx* c = (RoundCtx*)ctx;
@@ -315,20 +262,18 @@ extern "C" int bsc_round_audit_slot(void* ctx) {
 // The audit's commitment sums taken early, from the pre-step's per-peer chunk commitments instead of the
 // share MSM's commitment slots: as soon as the committee's selection has set the speculative rows' flags
 // (queued on main before main waits for the MSM), the side stream sums ccom[rows[r]] over the rows r
-// still alive -- the same rows the share sums use -- while the MSM is still running.  ccom: Jacobian
-// [npeer][nch][24], produced on another stream (ev_ccom).  bsc_round_secagg(.., audit = 2) then skips
-// its own commitment sums and bsc_round_audit waits for these.
+// still alive -- the same rows the share sums use -- while the MSM is still running.  p.ccom: Jacobian
+// [npeer][nch][24], produced on another stream (p.ev_ccom).  secagg / partials (audit = 2) then skip their
+// own commitment sums and bsc_round_audit waits for these.
 // `stream`: where the sums run -- NOT the side stream, which is still busy with the share MSM (they would
 // queue behind it); nullptr = the side stream.
-extern "C" int bsc_round_csum_early(void* ctx, const uint32_t* ccom, void* ev_ccom, const int* rows, int R,
-                                    const int* mask, uint32_t* cs, void* stream) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || R <= 0) return -1;
+static int csum_early(RoundCtx* c, const PreSlot& p, const int* rows, int R, const int* mask, uint32_t* cs,
+                      void* stream) {
   hipStream_t st = stream != nullptr ? (hipStream_t)stream : c->side;
   RC_CHECK(hipEventRecord(c->ev_main, c->main));
   RC_CHECK(hipStreamWaitEvent(st, c->ev_main, 0));
-  if (ev_ccom != nullptr) RC_CHECK(hipStreamWaitEvent(st, (hipEvent_t)ev_ccom, 0));
-  RC_CHECK(bsc_sum_rows2_pos(ccom, c->nch, rows, R, nullptr, c->nch, mask, cs, st));
+  if (p.ev_ccom != nullptr) RC_CHECK(hipStreamWaitEvent(st, p.ev_ccom, 0));
+  RC_CHECK(bsc_sum_rows2_pos(p.ccom, c->nch, rows, R, nullptr, c->nch, mask, cs, st));
   RC_CHECK(hipEventRecord(c->ev_side, st));
   return 0;
 }
@@ -415,65 +360,6 @@ extern "C" int bsc_round_spec_topup(void* ctx, int slot, const int* keep_host, i
   return 0;   // (the aggregation that reads the slot again re-marks it read: spec_mark_read)
 }
 
-// The next round's pre-step (head.py _queue_pre_step) in one call, queued behind everything on main so far
-// (the recovery of W):
-//   gram stream: local SGD step of every local peer (delta, qdelta, loss), event ev_step; then, when
-//                do_gram, the noise-aware Krum's phase-1 Gram of [delta; this iteration's noise rows],
-//                event ev_gram
-//   background:  behind the step, the per-chunk commitments of every row (ccom, event ev_ccom), their
-//                per-row sums = the full commitments (jac), read back into pinned jac_host, event ev_commit
-// Outputs are resident (the caller rotates them over slots); events are caller-owned and re-recorded.
-static int prestep_impl(RoundCtx* c, hipStream_t gs, const float* X, const int* y, const long long* off,
-                        const int* ntrain, const int* pid, const double* W, int d_in, int d_out, int B, int P,
-                        unsigned long long seed, int iteration, float max_norm, double qscale, int lo, float* delta,
-                        long long* qdelta, float* loss, const uint32_t* tbl_wb, const int* rows_arange, uint32_t* ccom,
-                        uint32_t* jac, uint32_t* jac_host, int do_gram, const float* T_rows, int U2, long long stride2,
-                        int kchunk, double* part, double* gram, unsigned int* counters, void* ev_step, void* ev_ccom,
-                        void* ev_commit, void* ev_gram, int chunked, hipStream_t cst, int* ones, int nones,
-                        hipEvent_t ones_wait, const double* nn) {
-  if (c == nullptr || P <= 0 || d_in * d_out + d_out != c->d) return -1;
-  RC_CHECK(hipEventRecord(c->ev_pre, c->main));
-  RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
-  if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
-  RC_CHECK(bsc_softmax_step_ones(X, y, off, ntrain, pid, W, d_in, d_out, B, P, seed, iteration, max_norm, qscale, delta,
-                                 qdelta, loss, lo, ones, nones, gs));
-  RC_CHECK(hipEventRecord((hipEvent_t)ev_step, gs));
-  RC_CHECK(hipStreamWaitEvent(cst, (hipEvent_t)ev_step, 0));
-  if (chunked) {
-    RC_CHECK(bsc_shares_msm(qdelta, c->d, rows_arange, P, c->tbl_pk, tbl_wb, c->poly, c->T, c->b0, c->nw, 1, nullptr,
-                            nullptr, 0, ccom, nullptr, cst));
-    RC_CHECK(hipEventRecord((hipEvent_t)ev_ccom, cst));
-    RC_CHECK(bsc_segment_sum_h(ccom, P, c->nch, 1, 0, jac, jac_host, cst));   // full commitments + host mirror
-  } else {   // full commitments only (1024-coefficient slabs; ccom is the slab-partials scratch)
-    RC_CHECK(bsc_commit_rows(qdelta, c->d, rows_arange, P, c->tbl_pk, c->b0, c->nw, ccom, jac, cst));
-    RC_CHECK(hipMemcpyAsync(jac_host, jac, (size_t)P * 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, cst));
-  }
-  RC_CHECK(hipEventRecord((hipEvent_t)ev_commit, cst));
-  if (do_gram) {
-    RC_CHECK(bsc_gram_stacked(delta, P, T_rows, U2, stride2, c->d, kchunk, part, gram, counters, nn, gs));
-    RC_CHECK(hipEventRecord((hipEvent_t)ev_gram, gs));
-  }
-  return 0;
-}
-
-extern "C" int bsc_round_prestep(void* ctx, void* gram_stream, const float* X, const int* y, const long long* off,
-                                 const int* ntrain, const int* pid, const double* W, int d_in, int d_out, int B, int P,
-                                 unsigned long long seed, int iteration, float max_norm, double qscale, int lo,
-                                 float* delta, long long* qdelta, float* loss, const uint32_t* tbl_wb,
-                                 const int* rows_arange, uint32_t* ccom, uint32_t* jac, uint32_t* jac_host,
-                                 int do_gram, const float* T_rows, int U2, long long stride2, int kchunk, double* part,
-                                 double* gram, unsigned int* counters, void* ev_step, void* ev_ccom, void* ev_commit,
-                                 void* ev_gram, int chunked, void* commit_stream) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr) return -1;
-  // the commitments' stream (default: background; an A/B passes one masked to the CUs the MSM leaves)
-  hipStream_t cst = commit_stream != nullptr ? (hipStream_t)commit_stream : c->bg;
-  return prestep_impl(c, (hipStream_t)gram_stream, X, y, off, ntrain, pid, W, d_in, d_out, B, P, seed, iteration,
-                      max_norm, qscale, lo, delta, qdelta, loss, tbl_wb, rows_arange, ccom, jac, jac_host, do_gram,
-                      T_rows, U2, stride2, kchunk, part, gram, counters, ev_step, ev_ccom, ev_commit, ev_gram, chunked,
-                      cst, nullptr, 0, nullptr, nullptr);
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Several ranks (one per GPU).  The aggregation's ONE all_gather moves a packed row per rank,
 //     [ cs: nch x 24 u32 | ys: nch x T int64 | clock: int64 | pad ]      (row_bytes: a multiple of 96)
@@ -482,98 +368,69 @@ extern "C" int bsc_round_prestep(void* ctx, void* gram_stream, const float* X, c
 // array (k_recover_w with a row stride sums and recovers).  No repacking on either side of the collective.
 // (The native path, bsc_round_agg_multi, gathers the same send row in two pieces -- [ys | clock] for the recovery
 // first, [cs] for the audit behind the early commitment sums -- into recv = [world][cs] + [world][ys | clock].)
-//
-// bsc_round_partials: this rank's partials of its kept rows, written straight into its send row -- the
-//   miners' share-value sums (main), the chunk-commitment sums (side, or already queued on another stream by
-//   bsc_round_csum_early into the same slot: audit = 2), the witness sums (background; per-rank, no
-//   consumer on the protocol path), the rank's clock; main then waits for the commitment sums, so the
-//   collective the caller issues next on main sees a complete row.  R = 0: no local rows (zero partials,
-//   the point at infinity for the commitment sums).
-// bsc_round_combine: on main, behind the collective: the commitment totals over the ranks (the audit's
-//   input), the fused share totals + exact recovery + W update, and the read-back of (status, W_new, every
-//   rank's clock) -- event `readback`.
 extern "C" int bsc_round_row_bytes(int nch, int T) {
   const long long raw = 96ll * nch + 8ll * nch * T + 8;
   return (int)((raw + 95) / 96 * 96);
 }
 
-static int partials_impl(void* ctx, const uint32_t* pts, int R, const long long* ys, const int* mask, const int* ccols,
-                         const int* wcols, int nwc, uint32_t* ws, unsigned char* send, long long clock, int audit,
-                         int wait_cs, int defer_wit = 0);
-
-extern "C" int bsc_round_partials(void* ctx, const uint32_t* pts, int R, const long long* ys, const int* mask,
-                                  const int* ccols, const int* wcols, int nwc, uint32_t* ws, unsigned char* send,
-                                  long long clock, int audit) {
-  return partials_impl(ctx, pts, R, ys, mask, ccols, wcols, nwc, ws, send, clock, audit, 1);
-}
-
-// wait_cs = 0: main does not wait for the commitment partials (the native path gathers them separately);
-// defer_wit = 1: no witness sums here (the caller queues them after the recovery: they have no consumer in the round)
-static int partials_impl(void* ctx, const uint32_t* pts, int R, const long long* ys, const int* mask, const int* ccols,
-                         const int* wcols, int nwc, uint32_t* ws, unsigned char* send, long long clock, int audit,
-                         int wait_cs, int defer_wit) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || R < 0) return -1;
+namespace {
+// This rank's partials of its R kept rows, written straight into its send row: the miners' share-value sums and
+// the rank's clock (main), the chunk-commitment sums (side, or already queued on another stream by csum_early
+// into the same slot: audit = 2), the witness sums (witness stream; per rank, no consumer on the protocol
+// path).  R = 0: no local rows (zero partials, the point at infinity for the commitment sums).
+// wait_cs = 1: main then waits for the commitment sums, so the collective the caller issues next on main sees a
+// complete row (0: the native path gathers them separately); defer_wit = 1: no witness sums here (the caller
+// queues them after the recovery: they have no consumer in the round)
+int partials(RoundCtx* c, const Layout& L, const uint32_t* pts, int R, const long long* ys, const int* mask,
+             unsigned char* send, long long clock, int audit, int wait_cs, int defer_wit) {
   const int nch = c->nch, T = c->T;
   uint32_t* cs_slot = (uint32_t*)send;
   long long* ys_slot = (long long*)(send + 96ll * nch);
-  unsigned char* clk = send + 96ll * nch + 8ll * nch * T;
   RC_CHECK(hipEventRecord(c->ev_main, c->main));
   if (R > 0) {
     const int ncols_in = nch * (T + 1);
     if (audit == 1) {
       RC_CHECK(hipStreamWaitEvent(c->side, c->ev_main, 0));
-      RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, ccols, nch, mask, cs_slot, c->side));
+      RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, L.ccols, nch, mask, cs_slot, c->side));
       RC_CHECK(hipEventRecord(c->ev_side, c->side));
     }
-    if (nwc > 0 && ws != nullptr && !defer_wit) {
+    if (L.nwc > 0 && L.ws != nullptr && !defer_wit) {
       RC_CHECK(hipStreamWaitEvent(c->wit, c->ev_main, 0));
-      RC_CHECK(bsc_sum_cols_serial(pts, ncols_in, R, wcols, nwc, mask, ws, c->wit));
+      RC_CHECK(bsc_sum_cols_serial(pts, ncols_in, R, L.wcols, L.nwc, mask, L.ws, c->wit));
       RC_CHECK(spec_mark_read(c, mask));
     }
   } else if (audit != 0) {
     RC_CHECK(hipMemsetAsync(cs_slot, 0, 96ull * nch, c->main));
   }
   // the share-value sums (zeros without local rows) and the clock right behind them, in one launch
-  if ((long long*)clk != ys_slot + (long long)nch * T) return -1;
-  RC_CHECK(bsc_sum_rows_i64_tail(R > 0 ? ys : nullptr, R > 0 ? R : 0, (long long)nch * T, R > 0 ? mask : nullptr,
-                                 ys_slot, clock, c->main));
+  RC_CHECK(bsc_sum_rows_i64_tail(R > 0 ? ys : nullptr, R, (long long)nch * T, R > 0 ? mask : nullptr, ys_slot, clock,
+                                 c->main));
   if (R > 0 && audit != 0 && wait_cs) RC_CHECK(hipStreamWaitEvent(c->main, c->ev_side, 0));
   return 0;
 }
 
-extern "C" int bsc_round_combine(void* ctx, const unsigned char* recv, int world, long long row_bytes,
-                                 const int* ycols, const int* xs, int npts, const long long* A, const int* basis,
-                                 int shift, unsigned long long inv_lo, unsigned long long inv_hi, const double* W,
-                                 double* W_new, long long* coeffs, int* status, long long* agg, uint32_t* cs,
-                                 int* h_status, double* h_W, long long* h_clock, int audit) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || world <= 0 || row_bytes % 96 != 0 || row_bytes < bsc_round_row_bytes(c->nch, c->T)) return -1;
+// On main, behind the collective into recv [world][row_bytes]: the commitment totals over the ranks (the
+// audit's input), the fused share totals + exact recovery + W update, which mirrors (status, W_new, every rank's
+// clock) to pinned memory itself -- event `readback`.
+int combine(RoundCtx* c, const Layout& L, const unsigned char* recv, int world, long long row_bytes, const double* W,
+            double* W_new, long long* h_clock, int audit) {
   const int nch = c->nch, T = c->T;
   if (audit != 0) {
-    RC_CHECK(bsc_sum_rows2((const uint32_t*)recv, (int)(row_bytes / 96), nullptr, world, nullptr, nch, nullptr, cs,
+    RC_CHECK(bsc_sum_rows2((const uint32_t*)recv, (int)(row_bytes / 96), nullptr, world, nullptr, nch, nullptr, c->cs,
                            c->main));
     RC_CHECK(hipEventRecord(c->ev_side, c->main));   // bsc_round_audit waits for the sums through ev_side
   }
-  // (every rank's clock is mirrored to h_clock by the recovery itself: no strided read-back copy behind it)
-  RC_CHECK(bsc_recover_w_clock((const long long*)(recv + 96ll * nch), world, row_bytes / 8, nch, T, nullptr, ycols, xs,
-                               npts, A, basis, c->poly, shift, inv_lo, inv_hi, c->d, W, c->qscale, W_new, coeffs, status,
-                               agg, h_W, h_status, h_clock, c->main));
+  RC_CHECK(bsc_recover_w_clock((const long long*)(recv + 96ll * nch), world, row_bytes / 8, nch, T, nullptr, L.ycols,
+                               L.xs, L.npts, L.A, L.basis, c->poly, L.shift, L.inv_lo, L.inv_hi, c->d, W, c->qscale,
+                               W_new, c->coeffs, c->status, L.agg, c->h_W, c->h_status, h_clock, c->main));
   RC_CHECK(hipEventRecord(c->ev_readback, c->main));
   return 0;
 }
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
-// Fused round calls.  The host loop of a round is its critical path; each Python-level launch with its
-// argument marshalling costs 5-60 us of it.  The buffers these calls use are registered once per run
-// (model ring, outputs, miner layouts, pre-step slots, the task), so one call per phase takes a handful of
-// arguments:
-//   bsc_round_after_select   behind the committee's selection (one rank): the speculative rows' flags
-//                            (k_set_alive), the early audit sums, the miners' sums + recovery + read-back,
-//                            the next round's pre-step, the audit -- what NativeSecAgg.secagg + prestep +
-//                            audit and four Python helpers did in ~130 us of host time
-//   bsc_round_select_partials / bsc_round_after_gather   the same on several ranks, split around the
-//                            aggregation's all_gather
+// The fused calls' resident state, registered once per run: model ring and outputs, miner layouts, the task,
+// pre-step slots.
 extern "C" int bsc_round_bind_outputs(void* ctx, double* const* W_ring, int nW, long long* coeffs, int* status,
                                       uint32_t* cs, int* ok, int* h_status, double* h_W, int* h_ok) {
   RoundCtx* c = (RoundCtx*)ctx;
@@ -693,23 +550,27 @@ extern "C" int bsc_ring_pick(const void* const* ring, int n, int* k, const void*
   return -1;
 }
 
-extern "C" int bsc_round_pick_W(void* ctx, const double* W) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || c->nW < 3) return -1;
+static int pick_W(RoundCtx* c, const double* W) {
+  if (c->nW < 3) return -1;
   return bsc_ring_pick((const void* const*)c->W_ring, c->nW, &c->Wk, W, (const void**)c->recent);
 }
 
-// the next round's pre-step into the next ring slot (noise-aware Gram when do_gram and a noise table is
-// bound; its rows for iteration `it` are the table's rows it % 100); returns the slot
+// The next round's pre-step (head.py _queue_pre_step) into the next ring slot, queued behind everything on main
+// so far (the recovery of W); returns the slot.
+//   gram stream: local SGD step of every local peer (delta, qdelta, loss), which also sets the next speculative
+//                slot's flags (after the slot's last reader), event ev_step; then, when do_gram and a noise
+//                table is bound, the noise-aware Krum's phase-1 Gram of [delta; the table's rows it % 100],
+//                event ev_gram
+//   background:  behind the step, the per-chunk commitments of every row (ccom, event ev_ccom), their
+//                per-row sums = the full commitments (jac) with the host mirror jac_host, event ev_commit
+// Outputs and events are the slot's (bsc_round_add_pre_slot); the events are caller-owned and re-recorded.
 extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do_gram) {
   RoundCtx* c = (RoundCtx*)ctx;
   if (c == nullptr || !c->task.bound || c->npre < 3) return -1;
   c->pre_k = (c->pre_k + 1) % c->npre;
   const PreSlot& p = c->pre[c->pre_k];
   const TaskCfg& t = c->task;
-  const bool g = do_gram && t.noise != nullptr;
-  const float* rows = g ? t.noise + (size_t)(it % 100) * c->d : nullptr;
-  // the next speculative slot's flags are set inside the step (after the slot's last reader)
+  hipStream_t gs = t.gram;
   int* ones = nullptr;
   hipEvent_t ones_wait = nullptr;
   if (c->nspec > 0) {
@@ -718,32 +579,70 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
     ones_wait = c->spec_used[ns] ? c->spec_done[ns] : nullptr;
     c->spec_filled[ns] = true;
   }
-  RC_CHECK(prestep_impl(c, t.gram, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it,
-                        t.max_norm, t.qs, t.lo, p.delta, p.qdelta, p.loss, t.tbl_wb, t.rows_arange, p.ccom, p.jac,
-                        p.jac_host, g ? 1 : 0, rows, g ? t.noise_n : 0, 100ll * c->d, t.kchunk, p.part, p.gram,
-                        t.counters, p.ev_step, p.ev_ccom, p.ev_commit, p.ev_gram, 1, c->bg, ones, c->spec_cap,
-                        ones_wait, g && t.nn_tab ? t.nn_tab + (size_t)(it % 100) * t.noise_n * t.noise_n : nullptr));
+  RC_CHECK(hipEventRecord(c->ev_pre, c->main));
+  RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
+  if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
+  RC_CHECK(bsc_softmax_step_ones(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.max_norm,
+                                 t.qs, p.delta, p.qdelta, p.loss, t.lo, ones, c->spec_cap, gs));
+  RC_CHECK(hipEventRecord(p.ev_step, gs));
+  RC_CHECK(hipStreamWaitEvent(c->bg, p.ev_step, 0));
+  RC_CHECK(bsc_shares_msm(p.qdelta, c->d, t.rows_arange, t.P, c->tbl_pk, t.tbl_wb, c->poly, c->T, c->b0, c->nw, 1,
+                          nullptr, nullptr, 0, p.ccom, nullptr, c->bg));
+  RC_CHECK(hipEventRecord(p.ev_ccom, c->bg));
+  RC_CHECK(bsc_segment_sum_h(p.ccom, t.P, c->nch, 1, 0, p.jac, p.jac_host, c->bg));
+  RC_CHECK(hipEventRecord(p.ev_commit, c->bg));
+  if (do_gram && t.noise != nullptr) {
+    const size_t k = (size_t)(it % 100);   // the noisers' pre-sampled vectors of this iteration
+    RC_CHECK(bsc_gram_stacked(p.delta, t.P, t.noise + k * c->d, t.noise_n, 100ll * c->d, c->d, t.kchunk, p.part, p.gram,
+                              t.counters, t.nn_tab ? t.nn_tab + k * t.noise_n * t.noise_n : nullptr, gs));
+    RC_CHECK(hipEventRecord(p.ev_gram, gs));
+  }
   return c->pre_k;
 }
 
+namespace {
 // the selection's flags for the speculative rows, then (early_slot >= 0) the audit's commitment sums from
 // that pre-step slot's chunk commitments into `cs_out`, then main waits for the MSM (spec_ev)
-static int select_head(RoundCtx* c, const int* node, const int* amap, int* alive, int nspec, const int* spec_rows,
-                       void* spec_ev, int early_slot, void* upload, uint32_t* cs_out) {
+int select_head(RoundCtx* c, const int* node, const int* amap, int* alive, int nspec, const int* spec_rows,
+                void* spec_ev, int early_slot, void* upload, uint32_t* cs_out) {
   // node == nullptr: the selection kernel has set the flags itself (k_krum_vote with amap / alive)
   if (nspec > 0 && node != nullptr) RC_CHECK(bsc_set_alive(node, amap, nspec, alive, c->main));
   if (early_slot >= 0) {
     if (early_slot >= c->npre || nspec <= 0) return -1;
-    const PreSlot& p = c->pre[early_slot];
-    RC_CHECK(bsc_round_csum_early(c, p.ccom, p.ev_ccom, spec_rows, nspec, alive, cs_out, upload));
+    RC_CHECK(csum_early(c, c->pre[early_slot], spec_rows, nspec, alive, cs_out, upload));
   }
   if (spec_ev != nullptr) RC_CHECK(hipStreamWaitEvent(c->main, (hipEvent_t)spec_ev, 0));
   return 0;
 }
 
-// One rank.  out[0] = model ring slot of the recovered model, out[1] = pre-step slot (-1: none queued).
-// pre_it >= 0 queues the next round's pre-step (iteration pre_it) behind the recovery; audit_now = 0 leaves
-// the audit to a later bsc_round_audit (the caller queues its own pre-step first).
+// Several ranks, before the aggregation's all_gather: flags, early audit sums and this rank's partials into
+// the send row (nspec = 0: no local rows).
+int select_partials(RoundCtx* c, const Layout& L, const int* node, const int* amap, int* alive, int nspec,
+                    const int* spec_rows, void* spec_ev, const uint32_t* pts, const long long* ys, int early_slot,
+                    void* upload, unsigned char* send, long long clock, int audit, int wait_cs, int defer_wit) {
+  RC_CHECK(select_head(c, node, amap, alive, nspec, spec_rows, nspec > 0 ? spec_ev : nullptr,
+                       audit == 2 && nspec > 0 ? early_slot : -1, upload, (uint32_t*)send));
+  return partials(c, L, pts, nspec, ys, alive, send, clock, audit, wait_cs, defer_wit);
+}
+
+// The fused calls' tail, behind the recovery into model ring slot wk: the next round's pre-step (pre_it >= 0:
+// its iteration), the audit (audit_now = 0 leaves it to a later bsc_round_audit: the caller queues its own
+// pre-step first).  out[0] = wk, out[1] = the pre-step's slot (-1: none queued).
+int queue_next(RoundCtx* c, int wk, int pre_it, int do_gram, int audit, int audit_now, int* out) {
+  int ps = -1;
+  if (pre_it >= 0) {
+    ps = bsc_round_prestep_slot(c, c->W_ring[wk], pre_it, do_gram);
+    if (ps < 0) return -3;
+  }
+  if (audit != 0 && audit_now) RC_CHECK(bsc_round_audit(c, c->coeffs, c->cs, c->ok, c->h_ok));
+  out[0] = wk;
+  out[1] = ps;
+  return 0;
+}
+}  // namespace
+
+// One rank, behind the committee's selection: the speculative rows' flags, the early audit sums, the miners'
+// sums + recovery + read-back, then the tail (queue_next: out, pre_it, audit_now).
 extern "C" int bsc_round_after_select(void* ctx, const int* node, const int* amap, int* alive, int nspec,
                                       const int* spec_rows, void* spec_ev, const uint32_t* pts, const long long* ys,
                                       int early_slot, void* upload, int layout, const double* W, int audit,
@@ -752,69 +651,34 @@ extern "C" int bsc_round_after_select(void* ctx, const int* node, const int* ama
   if (c == nullptr || layout < 0 || layout >= c->nlayouts || nspec <= 0 || c->nW < 3) return -1;
   const Layout& L = c->layouts[layout];
   RC_CHECK(select_head(c, node, amap, alive, nspec, spec_rows, spec_ev, audit == 2 ? early_slot : -1, upload, c->cs));
-  const int wk = bsc_round_pick_W(ctx, W);
+  const int wk = pick_W(c, W);
   if (wk < 0) return -2;
-  double* W_new = c->W_ring[wk];
-  RC_CHECK(bsc_round_secagg(ctx, pts, nspec, ys, alive, L.ccols, L.wcols, L.nwc, L.ycols, L.xs, L.npts, L.A, L.basis,
-                            L.shift, L.inv_lo, L.inv_hi, W, W_new, c->coeffs, c->status, L.agg, c->cs, L.ws,
-                            c->h_status, c->h_W, audit));
-  int ps = -1;
-  if (pre_it >= 0) {
-    ps = bsc_round_prestep_slot(ctx, W_new, pre_it, do_gram);
-    if (ps < 0) return -3;
-  }
-  if (audit != 0 && audit_now) RC_CHECK(bsc_round_audit(ctx, c->coeffs, c->cs, c->ok, c->h_ok));
-  out[0] = wk;
-  out[1] = ps;
-  return 0;
-}
-
-// Several ranks, before the aggregation's all_gather: flags, early audit sums and this rank's partials into
-// the send row (nspec = 0: no local rows).
-static int select_partials_impl(void* ctx, const int* node, const int* amap, int* alive, int nspec,
-                                 const int* spec_rows, void* spec_ev, const uint32_t* pts, const long long* ys,
-                                 int early_slot, void* upload, int layout, unsigned char* send, long long clock, int audit,
-                                 int wait_cs, int defer_wit = 0) {
-  RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || layout < 0 || layout >= c->nlayouts) return -1;
-  const Layout& L = c->layouts[layout];
-  RC_CHECK(select_head(c, node, amap, alive, nspec, spec_rows, nspec > 0 ? spec_ev : nullptr,
-                       audit == 2 && nspec > 0 ? early_slot : -1, upload, (uint32_t*)send));
-  return partials_impl(ctx, nspec > 0 ? pts : nullptr, nspec, nspec > 0 ? ys : nullptr, nspec > 0 ? alive : nullptr,
-                       L.ccols, L.wcols, nspec > 0 ? L.nwc : 0, L.ws, send, clock, nspec > 0 ? audit : (audit ? 1 : 0),
-                       wait_cs, defer_wit);
+  RC_CHECK(secagg(c, L, pts, nspec, ys, alive, W, c->W_ring[wk], audit));
+  return queue_next(c, wk, pre_it, do_gram, audit, audit_now, out);
 }
 
 extern "C" int bsc_round_select_partials(void* ctx, const int* node, const int* amap, int* alive, int nspec,
                                          const int* spec_rows, void* spec_ev, const uint32_t* pts, const long long* ys,
                                          int early_slot, void* upload, int layout, unsigned char* send, long long clock,
                                          int audit) {
-  return select_partials_impl(ctx, node, amap, alive, nspec, spec_rows, spec_ev, pts, ys, early_slot, upload, layout,
-                              send, clock, audit, 1);
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || layout < 0 || layout >= c->nlayouts || nspec < 0) return -1;
+  return select_partials(c, c->layouts[layout], node, amap, alive, nspec, spec_rows, spec_ev, pts, ys, early_slot,
+                         upload, send, clock, audit, 1, 0);
 }
 
-// Several ranks, behind the all_gather into recv: totals + recovery + read-back (clocks included), the next
-// pre-step (no Gram: the caller gathers the deltas and splits the Gram across ranks), the audit.
+// Several ranks, behind the all_gather into recv: totals + recovery + read-back (clocks included), then the tail
+// (no Gram in the pre-step: the caller gathers the deltas and splits the Gram across ranks).
 extern "C" int bsc_round_after_gather(void* ctx, const unsigned char* recv, int world, long long row_bytes, int layout,
                                       const double* W, long long* h_clock, int audit, int pre_it, int audit_now,
                                       int* out) {
   RoundCtx* c = (RoundCtx*)ctx;
   if (c == nullptr || layout < 0 || layout >= c->nlayouts) return -1;
-  const Layout& L = c->layouts[layout];
-  const int wk = bsc_round_pick_W(ctx, W);
+  if (world <= 0 || row_bytes % 96 != 0 || row_bytes < bsc_round_row_bytes(c->nch, c->T)) return -1;
+  const int wk = pick_W(c, W);
   if (wk < 0) return -2;
-  RC_CHECK(bsc_round_combine(ctx, recv, world, row_bytes, L.ycols, L.xs, L.npts, L.A, L.basis, L.shift, L.inv_lo,
-                             L.inv_hi, W, c->W_ring[wk], c->coeffs, c->status, L.agg, c->cs, c->h_status, c->h_W,
-                             h_clock, audit));
-  int ps = -1;
-  if (pre_it >= 0) {
-    ps = bsc_round_prestep_slot(ctx, c->W_ring[wk], pre_it, 0);
-    if (ps < 0) return -3;
-  }
-  if (audit != 0 && audit_now) RC_CHECK(bsc_round_audit(ctx, c->coeffs, c->cs, c->ok, c->h_ok));
-  out[0] = wk;
-  out[1] = ps;
-  return 0;
+  RC_CHECK(combine(c, c->layouts[layout], recv, world, row_bytes, W, c->W_ring[wk], h_clock, audit));
+  return queue_next(c, wk, pre_it, 0, audit, audit_now, out);
 }
 
 // Host wait for an event: spin for SPIN_NS (the round's waits are tens to a few hundred us, and a sleeping
@@ -1024,7 +888,9 @@ extern "C" int bsc_round_agg_multi(void* ctx, const int* node, const int* amap, 
                                    int early_slot, void* upload, int layout, long long clock, const double* W,
                                    int audit, int pre_it, int audit_now, int gram, int* out) {
   RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr || !c->m.bound || c->cworld < 2 || layout < 0 || layout >= c->nlayouts || upload == nullptr) return -1;
+  if (c == nullptr || !c->m.bound || c->cworld < 2 || layout < 0 || layout >= c->nlayouts || upload == nullptr ||
+      nspec < 0)
+    return -1;
   const Layout& L = c->layouts[layout];
   const int nch = c->nch, T = c->T, world = c->cworld;
   // two gathers out of the one send row [cs | ys | clock]: the share sums + clocks (the recovery's input) first, on
@@ -1036,11 +902,11 @@ extern "C" int bsc_round_agg_multi(void* ctx, const int* node, const int* amap, 
   unsigned char* recv_ys = c->m.recv + (size_t)world * cs_bytes;
   // issue order = the critical path first: partials -> share-sum gather -> recovery; then what only the audit, the
   // witness sums and the next round read (the host issues ~5 us per launch: the recovery no longer queues behind them)
-  RC_CHECK(select_partials_impl(ctx, node, amap, alive, nspec, spec_rows, spec_ev, pts, ys, early_slot, upload, layout,
-                                c->m.send, clock, audit, 0, 1));
+  RC_CHECK(select_partials(c, L, node, amap, alive, nspec, spec_rows, spec_ev, pts, ys, early_slot, upload, c->m.send,
+                           clock, audit, 0, 1));
   RC_CHECK(hipEventRecord(c->ev_main, c->main));   // the partials (or, no local rows, the zeroed commitment slot)
   RC_CHECK(round_all_gather(c, c->m.send + cs_bytes, recv_ys, ys_bytes, c->main, c->main));
-  const int wk = bsc_round_pick_W(ctx, W);
+  const int wk = pick_W(c, W);
   if (wk < 0) return -2;
   RC_CHECK(bsc_recover_w_clock((const long long*)recv_ys, world, (long long)(ys_bytes / 8), nch, T, nullptr, L.ycols, L.xs,
                                L.npts, L.A, L.basis, c->poly, L.shift, L.inv_lo, L.inv_hi, c->d, W, c->qscale,
@@ -1059,25 +925,10 @@ extern "C" int bsc_round_agg_multi(void* ctx, const int* node, const int* amap, 
     RC_CHECK(bsc_sum_cols_serial(pts, nch * (T + 1), nspec, L.wcols, L.nwc, alive, L.ws, c->wit));
     RC_CHECK(spec_mark_read(c, alive));
   }
-  int ps = -1;
-  if (pre_it >= 0) {
-    ps = bsc_round_prestep_slot(ctx, c->W_ring[wk], pre_it, 0);
-    if (ps < 0) return -3;
-  }
-  if (audit != 0 && audit_now) RC_CHECK(bsc_round_audit(ctx, c->coeffs, c->cs, c->ok, c->h_ok));
-  out[0] = wk;
-  out[1] = ps;
-  if (ps >= 0 && gram) RC_CHECK(round_multi_gram(c, ps, pre_it));
+  RC_CHECK(queue_next(c, wk, pre_it, 0, audit, audit_now, out));
+  if (out[1] >= 0 && gram) RC_CHECK(round_multi_gram(c, out[1], pre_it));
   return 0;
 }
-
-extern "C" int bsc_vg_pack(uint8_t* row, long long commit_off, long long nz_off, long long sc_off,
-                           const uint32_t* commits, int maxlocal, int pw, const int* src_row, const int* nz,
-                           const float* sc, int nnz, void* stream);
-extern "C" int bsc_vg_unpack(const uint8_t* recv, long long row_bytes, int chunk, int npairs, long long commit_off,
-                             long long nz_off, long long sc_off, int maxlocal, int pw, int nn, int world,
-                             const int* wrow, int nw, double* gram, int* nz, float* sc, uint32_t* commits_host,
-                             void* stream);
 
 // The verification row of iteration `it` (ops/gather.py): pack this rank's row, all_gather in place, unpack, on
 // `stream`; the Gram slot at the row's head was written by round_multi_gram (or the caller's Gram launch)

@@ -24,14 +24,11 @@ SIGNATURES = {
     "bsc_segment_sum": [P, I, I, I, I, P, P],
     "bsc_sum_rows2": [P, I, P, I, P, I, P, P, P],
     "bsc_sum_rows2_pos": [P, I, P, I, P, I, P, P, P],
-    "bsc_round_csum_early": [P, P, P, P, I, P, P, P],
     "bsc_round_spec_msm2": [P, I, P, P, P, I, P, I, I, P, P, P, P, P, P],
     "bsc_round_spec_topup": [P, I, P, I, P, I, P, P, I, I, P, P, P, P, P],
     "bsc_round_set_spec_ring": [P, P, I, I],
     "bsc_round_set_witness_stream": [P, P],
     "bsc_wave_prio": [I],
-    "bsc_round_prestep": [P, P, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, I, P, P, P, P, P, P, P, P,
-                          I, P, I, L, I, P, P, P, P, P, P, P, I, P],
     "bsc_commit_rows": [P, I, P, I, P, I, I, P, P, P],
     "bsc_stream_create_cumask": [I, P],
     "bsc_stream_destroy": [P],
@@ -69,23 +66,18 @@ SIGNATURES = {
     "bsc_lsh_count": [P, I, P, I, P, I, D, P, P],
     "bsc_weighted_rows": [P, I, I, P, P, P],
     "bsc_recover_w": [P, I, I, I, P, P, P, I, P, P, I, I, U64, U64, I, P, D, P, P, P, P, P],
-    "bsc_recover_w_strided": [P, I, L, I, I, P, P, P, I, P, P, I, I, U64, U64, I, P, D, P, P, P, P, P],
     # round.hip
     "bsc_round_create": [P, P, P, P, I, I, I, I, I, D],
     "bsc_round_destroy": [P],
-    "bsc_round_secagg": [P, P, I, P, P, P, P, I, P, P, I, P, P, I, U64, U64, P, P, P, P, P, P, P, P, P, I],
     "bsc_round_audit": [P, P, P, P, P],
     "bsc_round_wait": [P, I],
     "bsc_round_audit_slot": [P],
     "bsc_set_host_spin_ns": [L],
     "bsc_round_row_bytes": [I, I],
-    "bsc_round_partials": [P, P, I, P, P, P, P, I, P, P, L, I],
-    "bsc_round_combine": [P, P, I, L, P, P, I, P, P, I, U64, U64, P, P, P, P, P, P, P, P, P, I],
     "bsc_round_bind_outputs": [P, P, I, P, P, P, P, P, P, P],
     "bsc_round_add_layout": [P, P, P, I, P, P, I, P, P, I, U64, U64, P, P],
     "bsc_round_bind_task": [P, P, P, P, P, P, P, I, I, I, I, U64, F, D, I, P, P, P, I, I, P],
     "bsc_round_add_pre_slot": [P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "bsc_round_pick_W": [P, P],
     "bsc_round_prestep_slot": [P, P, I, I],
     "bsc_round_set_nn_table": [P, P],
     "bsc_round_after_select": [P, P, P, P, I, P, P, P, P, I, P, I, P, I, I, I, I, P],

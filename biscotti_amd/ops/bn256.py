@@ -391,7 +391,7 @@ class NativeSecAgg:
       prestep          the pre-step alone (first round, host-decided rounds)
 
     A recovered model never lands in the buffer it is computed from nor in one of the last two results
-    (bsc_round_pick_W): aggregates that are computed and then dropped (speculative misses, failed audits,
+    (bsc_ring_pick): aggregates that are computed and then dropped (speculative misses, failed audits,
     empty blocks) cannot overwrite the live model."""
 
     W_RING = 4

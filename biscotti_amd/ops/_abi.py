@@ -66,6 +66,8 @@ SIGNATURES = {
     "bsc_lsh_count": [P, I, P, I, P, I, D, P, P],
     "bsc_weighted_rows": [P, I, I, P, P, P],
     "bsc_recover_w": [P, I, I, I, P, P, P, I, P, P, I, I, U64, U64, I, P, D, P, P, P, P, P],
+    "bsc_recover_w_clock": [P, I, L, I, I, P, P, P, I, P, P, I, I, U64, U64, I, P, D, P, P, P, P, P, P, P, P],
+    "bsc_sum_rows_i64_tail": [P, I, L, P, P, L, P],
     # round.hip
     "bsc_round_create": [P, P, P, P, I, I, I, I, I, D],
     "bsc_round_destroy": [P],

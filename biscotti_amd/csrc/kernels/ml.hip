@@ -1200,6 +1200,78 @@ extern "C" __global__ void __launch_bounds__(256) k_roni_counts(const float* X, 
 }
 
 // =====================================================================================
+// Logistic scoring (creditcard: logistic_model.py's sign(X w) != y), for the evaluation and for committee RONI:
+// counts[m][s] = #rows of set s (rows [0, split): 0, rows [split, N): 1) with sign(x . w_m) != y, sign(0) = 0
+// counting as wrong like torch.sign.  Model 0 is W; model m >= 1 is W[k] + (double)U[sel[m - 1]][k], the sum
+// formed in fp64 per feature (the host loop's `W + X[i].double()`); a sel entry outside [0, n_cand) scores as W.
+// One block per (LC_ROWS rows, LC_MODELS models): the block's models are staged in LDS zero-padded to LC_DMAX
+// features, every lane keeps one row in registers and takes a sequential fp64 FMA dot per model (the padding
+// adds exact zeros); a wave ballot per model gives that wave's misses of either set, kept in lane j for the
+// block's model j, then one atomic per (wave, model, set).  The work is ~9000 x 25 x 37 at the RONI shape --
+// latency, not throughput: 128-row blocks put that shape on 71 x 3 = 213 blocks, one wave of blocks over the CUs.
+// ahead: the evaluation's priority class (k_eval_error_t); RONI runs at the default like k_roni_counts.
+// =====================================================================================
+#define LC_ROWS 128
+#define LC_MODELS 16
+#define LC_DMAX 32
+extern "C" __global__ void __launch_bounds__(LC_ROWS) k_logit_counts(const double* X, const double* y, int N, int D,
+                                                                     int split, const double* W, const float* U,
+                                                                     int n_cand, const int* sel, int M, int ahead,
+                                                                     unsigned int* counts) {
+  if (ahead) BSC_SET_PRIO(BSC_PRIO_AHEAD);
+  __shared__ double wm[LC_MODELS][LC_DMAX];
+  const int lane = threadIdx.x & 63;
+  const int m0 = blockIdx.y * LC_MODELS, nm = min(LC_MODELS, M - m0);
+  const long long row = (long long)blockIdx.x * LC_ROWS + threadIdx.x;
+  const bool valid = row < N;
+  const size_t rl = (size_t)min(row, (long long)N - 1);   // lanes past N load the last row and are not counted
+  const double* xr = X + rl * D;
+  double x[LC_DMAX];
+#pragma unroll
+  for (int k = 0; k < LC_DMAX; ++k) x[k] = k < D ? xr[k] : 0.0;
+  const double yr = y[rl];
+  // the models: thread t forms feature t % LC_DMAX of models t / LC_DMAX + 4 i (every candidate index first, then
+  // every update: two dependent global latencies for the block, under the row loads)
+  constexpr int kPer = LC_MODELS * LC_DMAX / LC_ROWS, kStep = LC_ROWS / LC_DMAX;
+  static_assert(LC_ROWS % LC_DMAX == 0 && kPer * kStep == LC_MODELS && LC_MODELS <= 64, "staging covers wm once");
+  const int wk = threadIdx.x % LC_DMAX, wj = threadIdx.x / LC_DMAX;
+  const bool kin = wk < D;
+  const double wbase = kin ? W[wk] : 0.0;
+  int c[kPer];
+#pragma unroll
+  for (int i = 0; i < kPer; ++i) {
+    const int j = wj + i * kStep, m = m0 + j;
+    c[i] = (kin && j < nm && m > 0) ? sel[m - 1] : -1;
+  }
+#pragma unroll
+  for (int i = 0; i < kPer; ++i) {
+    const int j = wj + i * kStep;
+    double w = j < nm ? wbase : 0.0;
+    if (c[i] >= 0 && c[i] < n_cand) w += (double)U[(size_t)c[i] * D + wk];
+    wm[j][wk] = w;
+  }
+  const unsigned long long set0 = __ballot(valid && row < split), set1 = __ballot(valid && row >= split);
+  __syncthreads();
+  unsigned int c0 = 0, c1 = 0;
+  for (int j = 0; j < nm; ++j) {
+    double z = 0.0;
+#pragma unroll
+    for (int k = 0; k < LC_DMAX; ++k) z = __builtin_fma(x[k], wm[j][k], z);
+    const double s = (double)((z > 0.0) - (z < 0.0));
+    const unsigned long long miss = __ballot(!(s == yr) || z != z);
+    if (lane == j) {
+      c0 = (unsigned int)__popcll(miss & set0);
+      c1 = (unsigned int)__popcll(miss & set1);
+    }
+  }
+  if (lane < nm) {
+    unsigned int* out = counts + (size_t)(m0 + lane) * 2;
+    if (c0) atomicAdd(out, c0);
+    if (c1) atomicAdd(out + 1, c1);
+  }
+}
+
+// =====================================================================================
 // K12: exact recovery of the aggregated chunk polynomials from miner shares.
 // ys: int64 [nchunks][npts], xs: int [npts] distinct; deg+1 <= npts.  Newton divided differences
 // in 128-bit on the deg+1 nodes of smallest |x|, verified against every share.  Writes the
@@ -1666,6 +1738,27 @@ extern "C" int bsc_roni_counts_rb(const float* X, const int* y, long long NX, in
   if (hipMemsetAsync(counts, 0, bytes, s) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_roni_counts, dim3(ni + 1, V, tiles), dim3(256), 0, s, X, y, NX, D_IN, D_OUT, W, U, n_cand, rows,
                      nrows, Bmax, cand, ni, transform, counts);
+  const int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  return (int)hipMemcpyAsync(counts_host, counts, bytes, hipMemcpyDeviceToHost, s);
+}
+
+// logistic scoring: counters zeroed, k_logit_counts, and the [M, 2] counts' read-back into pinned memory, all on
+// `stream`.  M models: W and the M - 1 rows of U that sel names.  M == 1 is the evaluation (its priority class);
+// more models are a RONI committee.  No row: nothing is launched (the host buffer is not written).
+extern "C" int bsc_logit_counts_rb(const double* X, const double* y, int N, int D, int split, const double* W,
+                                   const float* U, int n_cand, const int* sel, int M, unsigned int* counts,
+                                   unsigned int* counts_host, void* stream) {
+  if (D <= 0 || D > LC_DMAX || N < 0 || split < 0 || split > N || M < 1) return -1;
+  if (M > 1 && (n_cand <= 0 || U == nullptr || sel == nullptr)) return -1;
+  if (N == 0) return 0;
+  const int mtiles = (M + LC_MODELS - 1) / LC_MODELS;
+  if (mtiles > 65535) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)M * 2 * sizeof(unsigned int);
+  if (hipMemsetAsync(counts, 0, bytes, s) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_logit_counts, dim3((unsigned int)(((long long)N + LC_ROWS - 1) / LC_ROWS), mtiles),
+                     dim3(LC_ROWS), 0, s, X, y, N, D, split, W, U, n_cand, sel, M, M == 1 ? 1 : 0, counts);
   const int rc = (int)hipGetLastError();
   if (rc != 0) return rc;
   return (int)hipMemcpyAsync(counts_host, counts, bytes, hipMemcpyDeviceToHost, s);

@@ -169,6 +169,11 @@ class LogisticTask:
         self.yv = torch.from_numpy(cd.yvalid).to(self.device)
         self.Xt = torch.from_numpy(cd.X).to(self.device)
         self.yt = torch.from_numpy(cd.y).to(self.device)
+        # train | validation rows back to back, row-major (the loader's arrays keep its own layout): both metrics
+        # come from one kernel launch + one read-back, and the RONI committee scores the rows from eval_split on
+        self.eval_X = torch.cat([self.Xt, self.Xv]).contiguous()
+        self.eval_y = torch.cat([self.yt, self.yv]).contiguous()
+        self.eval_split = int(self.Xt.shape[0])
         assert self.peers == list(range(self.peers[0], self.peers[0] + len(self.peers))), "local peers are contiguous"
         self._local_index = {p: i for i, p in enumerate(self.peers)}
 
@@ -194,16 +199,53 @@ class LogisticTask:
         return float((yhat != y).sum()) / y.numel()
 
     def evaluate_async(self, W: torch.Tensor):
-        v = self.evaluate(W)
-        return lambda: v
+        """Queue the evaluation now; the returned callable reads it back.  logistic_model_test.py: train_error on
+        credittrain (logged as test_error), test_error on credittest (valid_error)."""
+        if self.device.type != "cuda":
+            v = {"test_error": self._err(self.Xt, self.yt, W), "valid_error": self._err(self.Xv, self.yv, W),
+                 "attack_rate": 0.0}
+            def done():
+                return v
+            done.ready = lambda: True
+            return done
+        both = K.logit_counts_async(self.eval_X, self.eval_y, self.eval_split, W)   # one launch, one read-back
+        nt, nv = self.eval_split, self.eval_X.shape[0] - self.eval_split
+
+        def result():
+            c = both()
+            return {"test_error": int(c[0, 0]) / nt, "valid_error": int(c[0, 1]) / nv, "attack_rate": 0.0}
+        result.ready = both.ready
+        return result
 
     def evaluate(self, W: torch.Tensor) -> dict:
-        # logistic_model_test.py: train_error on credittrain, test_error on credittest
-        return {"test_error": self._err(self.Xt, self.yt, W), "valid_error": self._err(self.Xv, self.yv, W),
-                "attack_rate": 0.0}
+        return self.evaluate_async(W)()
 
     def train_error(self, W: torch.Tensor, peer: int, iteration: int) -> float:
         return self._err(self.Xv, self.yv, W)
+
+    def roni_committee_async(self, W: torch.Tensor, U: torch.Tensor, cand: np.ndarray):
+        """RONI's error counts for the local verifiers at once (GPU).  Every verifier judges with the same
+        validation rows (train_error ignores the peer), so they are scored ONCE under W and under W + U[c] for
+        every distinct candidate c of the inboxes, in one launch (K.logit_counts_async).  U fp32 [n_cand, D]: the
+        candidate updates; cand int [V, ni]: the row of U in each inbox slot.  Returns a callable giving (counts
+        uint32 [V, ni + 1], nrows [V]) in K.roni_accept's form: column 0 the misses under W, column 1 + j under
+        W + U[cand[v, j]] -- train_error's count per (verifier, model) -- and nrows = the validation rows."""
+        cand = np.asarray(cand, np.int64)
+        V = cand.shape[0]
+        nv = int(self.Xv.shape[0])
+        uniq, slot = np.unique(cand, return_inverse=True)   # the distinct candidates; inbox slot -> its model - 1
+        sel = h2d(uniq, torch.int32, self.device)
+        # the validation rows of the resident evaluation buffer (row-major), as set 1 of an empty set 0
+        wait = K.logit_counts_async(self.eval_X[self.eval_split:], self.eval_y[self.eval_split:], 0, W, U, sel)
+
+        def result():
+            per_model = wait()[:, 1]                        # set 1: every row (split == 0)
+            counts = np.empty((V, cand.shape[1] + 1), np.uint32)
+            counts[:, 0] = per_model[0]
+            counts[:, 1:] = per_model[1 + slot.reshape(cand.shape)]
+            return counts, [nv] * V
+        result.ready = wait.ready
+        return result
 
 
 def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, **kw):

@@ -770,6 +770,73 @@ def roni_committee(X, y, rows, nrows, W, U, cand, d_in, d_out, transform=True) -
     return roni_committee_async(X, y, rows, nrows, W, U, cand, d_in, d_out, transform)()
 
 
+LOGIT_MAX_D = 32   # kernels/ml.hip LC_DMAX: features (bias column included) k_logit_counts keeps per lane
+LOGIT_ROWS, LOGIT_MODELS = 128, 16   # LC_ROWS, LC_MODELS: rows and models (the base model included) of one block
+_LOGIT_DEV: dict = {}   # pinned read-back buffer -> its device counters (persistent pairs)
+
+
+def _landed(value):
+    """A result that needs no wait, in the form of the queued ones (a callable with .ready)."""
+    def result():
+        return value
+    result.ready = lambda: True
+    return result
+
+
+def logit_counts_async(X, y, split: int, W, U=None, sel=None):
+    """Miss counts of the logistic model (sign(X w) != y, creditcard) under W and under W + U[sel[j]] on two row
+    sets, from ONE kernel launch and one read-back (k_logit_counts).
+
+    X fp64 [N, D] with the bias column, y fp64 [N] (+-1); rows [0, split) are set 0, rows [split, N) set 1; W fp64
+    [D]; U fp32 [n_cand, D] and sel int32 [M - 1], both optional: model 0 is W, model 1 + j is W + U[sel[j]].double()
+    (a sel entry outside [0, n_cand) scores as W).  Returns a callable giving counts, a numpy uint32 [M, 2]:
+    counts[m, s] = rows of set s that model m gets wrong; sign(0) = 0 is wrong, as with torch.sign.  The evaluation
+    is M == 1 (test | validation rows back to back), a RONI committee split == 0 with one model per candidate."""
+    N, D = X.shape
+    nsel = sel.numel() if sel is not None else 0
+    M = 1 + nsel
+    if not (0 < D <= LOGIT_MAX_D and 0 <= split <= N and W.numel() == D and y.numel() == N):
+        raise RuntimeError(f"logit_counts: out of contract (N={N}, D={D}, split={split}, |W|={W.numel()})")
+    if nsel and (U is None or U.dim() != 2 or U.shape[0] <= 0 or U.shape[1] != D):
+        raise RuntimeError("logit_counts: sel needs candidate rows U [n_cand, D]")
+    if N == 0:
+        return _landed(np.zeros((M, 2), np.uint32))
+    if X.device.type != "cuda":
+        Wn = W.double().cpu().numpy()
+        models = np.repeat(Wn[None, :], M, 0)
+        if nsel:
+            Un, sl = U.cpu().numpy(), sel.cpu().numpy().astype(np.int64)
+            ok = (sl >= 0) & (sl < Un.shape[0])
+            models[1:][ok] = Wn[None, :] + Un[sl[ok]].astype(np.float64)
+        Xn, yn = X.cpu().numpy(), y.cpu().numpy()
+        miss = np.sign(Xn @ models.T) != yn[:, None]   # [N, M]
+        return _landed(np.stack([miss[:split].sum(0), miss[split:].sum(0)], 1).astype(np.uint32))
+    assert X.dtype == torch.float64 and y.dtype == torch.float64 and W.dtype == torch.float64
+    if nsel:
+        assert U.dtype == torch.float32 and sel.dtype == torch.int32
+    # the pinned buffer rotates (lazy_eval reads an evaluation up to a few rounds later; a committee's counts may
+    # still be unread when the next is queued); its device counters rotate with it
+    host = pinned("logit", (M, 2), torch.int32, depth=4)
+    dev = _LOGIT_DEV.get(host.data_ptr())
+    if dev is None:
+        dev = _LOGIT_DEV[host.data_ptr()] = torch.zeros((M, 2), dtype=torch.int32, device=X.device)
+    _check(hip().bsc_logit_counts_rb(_p(X), _p(y), N, D, int(split), _p(W), _p(U) if nsel else None,
+                                     U.shape[0] if nsel else 0, _p(sel) if nsel else None, M, _p(dev),
+                                     host.data_ptr(), _stream()), "logit_counts")
+    ev = S.record()
+
+    def result():
+        S.host_wait(ev)
+        return host.numpy().view(np.uint32).copy()
+    result.ready = ev.query
+    return result
+
+
+def logit_counts(X, y, split: int, W, U=None, sel=None) -> np.ndarray:
+    """logit_counts_async, read back at once: counts uint32 [M, 2]."""
+    return logit_counts_async(X, y, split, W, U, sel)()
+
+
 def roni_accept(counts, nrows, threshold: float = 0.02) -> np.ndarray:
     """RONI's decision from the committee's counts: bool [V, ni], slot j of verifier v accepted iff its training
     error under the update exceeds the base model's by at most `threshold` (VerifyUpdateRONI, main.go:191-233) --

@@ -234,11 +234,19 @@ class VerifyMixin:
         """RONI for every local verifier at once (k_roni_counts): each verifier's minibatch under W and under
         W + every row of its inbox in ONE launch with one read-back, instead of _verify's launch and wait per
         (verifier, candidate).  The same error counts bit for bit, so the same decisions.  X: the candidate
-        rows, xrow: worker -> row of X.  Returns bool [len(local_vs), ni], or None where it does not apply (CPU,
-        a task without roni_rows such as creditcard, the collusion experiment, no local verifier): the caller
-        then takes the _verify loop."""
-        if not (self.gpu and local_vs and self.cfg.colluders == 0 and hasattr(self.task, "roni_rows")):
+        rows, xrow: worker -> row of X.  The logistic task (creditcard) scores its validation rows the same way
+        through its own entry point (k_logit_counts: the verifiers share those rows, so each distinct candidate is
+        scored once).  Returns bool [len(local_vs), ni], or None where it does not apply (CPU, the collusion
+        experiment, no local verifier, a task with neither entry point): the caller then takes the _verify loop."""
+        if not (self.gpu and local_vs and self.cfg.colluders == 0):
             return None
+        if not hasattr(self.task, "roni_rows"):
+            if not hasattr(self.task, "roni_committee_async"):
+                return None
+            cand_np = np.asarray([[xrow[w] for w in inboxes[v]] for v in local_vs], np.int32)
+            with self.timer.phase("verify.defense"):
+                counts, nrows = self.task.roni_committee_async(self.W, X.contiguous(), cand_np)()
+            return K.roni_accept(counts, nrows)
         rows_np, nrows_np = self.task.roni_rows(local_vs, it)
         if not nrows_np.all():   # an empty shard: train_error's 0.0 convention stays with the loop
             return None
@@ -471,7 +479,7 @@ class VerifyMixin:
                 if ok_all is not None:
                     for k, v in enumerate(local_vs):
                         mine[plan.verifiers.index(v)] = ok_all[k]
-                else:   # CPU, creditcard, the collusion experiment: one verifier and one candidate at a time
+                else:   # CPU, the collusion experiment: one verifier and one candidate at a time
                     for v in local_vs:
                         rows_v = h2d([xrow[w] for w in inboxes[v]], torch.long, self.dev)
                         with tm.phase("verify.defense"):

@@ -2,6 +2,8 @@
 // computes but never consumes: the roles proof of getVRFRoles (quirk Q7) and the proof half of every
 // worker's noiser VRF (vrf.go:54-100; the lottery reads only the 64-byte output, which the host
 // computes on the critical path).  The host runtime (runtime/vrf.cpp) is the bit-exact oracle.
+// By default nothing reads these proofs; with the opt-in audit (RunConfig.vrf_audit, --vrf-audit) the batched
+// verifier at the end of this file (k_vrf_verify) checks every one of them in place, right behind the prover.
 //
 // Latency, not throughput, is what matters: a round submits ~200 proofs (a few waves on a 1024-SIMD
 // chip) and the last round's proofs must finish before a timed run ends.  A proof's work is therefore
@@ -406,14 +408,16 @@ __device__ void signed_digits(int8_t e[64], const uint32_t k[8]) {
   e[63] = (int8_t)(e[63] + carry);
 }
 // k * P with P's table (1P..8P, cached) already in `tbl` (global scratch of this thread)
+// nd: the signed digits of k that can be non-zero (64; 33 for a 128-bit k: 32 digits and the last carry) --
+// the windows above them would only double the identity
 // not inlined: waves 0 and 1 of a workgroup run this one copy (x H and k H) from the instruction cache
-__device__ __attribute__((noinline)) ge ge_mul_tbl(const uint32_t* tbl, const uint32_t k[8]) {
+__device__ __attribute__((noinline)) ge ge_mul_tbl(const uint32_t* tbl, const uint32_t k[8], int nd) {
   int8_t e[64];
   signed_digits(e, k);
   ge r = ge_identity();
 #pragma unroll 1
-  for (int w = 63; w >= 0; --w) {
-    if (w != 63) {
+  for (int w = nd - 1; w >= 0; --w) {
+    if (w != nd - 1) {
 #pragma unroll 1
       for (int j = 0; j < 4; ++j) r = ge_dbl(r, j == 3);
     }
@@ -578,6 +582,70 @@ __device__ __forceinline__ uint32_t le_word(const uint8_t* d, int i) {
   return (uint32_t)d[4 * i] | ((uint32_t)d[4 * i + 1] << 8) | ((uint32_t)d[4 * i + 2] << 16) | ((uint32_t)d[4 * i + 3] << 24);
 }
 
+// Phase 1 of the prover and of the verifier: the first try-and-increment candidate of (pk, alpha) that decodes
+// (before the cofactor), 12 counters per proof tried at once.  Every thread of the workgroup calls it and walks
+// the same barriers; `active`: this lane's proof takes part (the lanes of a proof agree).  Returns whether the
+// proof has a candidate; its affine (x, y) is then in s_h[p].
+__device__ __forceinline__ bool h2c_candidate(bool active, const uint32_t pk[8], const uint8_t* alpha, int alpha_len,
+                                              const fe& d, int slot, int p, int (*s_ok)[VP], int* s_win,
+                                              uint32_t (*s_h)[20]) {
+  if (threadIdx.x < VP) s_win[threadIdx.x] = -1;
+  for (int base = 0; base < 256; base += VTRY) {
+    const int ctr = base + slot;
+    ge cand;
+    bool ok = false;
+    __syncthreads();
+    if (active && s_win[p] < 0 && ctr < 256) {
+      Sha512 sh;
+      sha_init(sh);
+      sha_byte(sh, SUITE);
+      sha_byte(sh, 0x01);
+      sha_words(sh, pk, 8);
+      sha_bytes(sh, alpha, alpha_len);
+      sha_byte(sh, (uint8_t)ctr);
+      sha_byte(sh, 0x00);
+      uint8_t dig[64];
+      sha_final(sh, dig);
+      ok = ge_frombytes(cand, dig, d);
+    }
+    s_ok[slot][p] = ok ? 1 : 0;
+    __syncthreads();
+    if (ok && s_win[p] < 0) {
+      int first = slot;
+      for (int j = 0; j < slot; ++j)
+        if (s_ok[j][p]) { first = j; break; }
+      if (first == slot) {   // the smallest decoding counter of this proof: publish H
+        st_fe(&s_h[p][0], cand.X);
+        st_fe(&s_h[p][10], cand.Y);
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < VP) {
+      int first = -1;
+      for (int j = 0; j < VTRY && first < 0; ++j)
+        if (s_ok[j][threadIdx.x]) first = j;
+      if (first >= 0 && s_win[threadIdx.x] < 0) s_win[threadIdx.x] = base + first;
+    }
+    __syncthreads();
+    // (threads 0..15 are lane p = threadIdx.x of their proof: `active` is that proof's)
+    const int pending = (threadIdx.x < VP && active && s_win[threadIdx.x] < 0) ? 1 : 0;
+    if (!__syncthreads_or(pending)) break;
+  }
+  return active && s_win[p] >= 0;
+}
+// the cached multiples 1P..8P of P into `tbl` (320 words of global scratch)
+__device__ __forceinline__ void ge_table(uint32_t* tbl, const ge& P, const fe& d2) {
+  const gc c1 = ge_cache(P, d2);
+  st_gc(tbl, c1);
+  ge acc = ge_dbl(P, true);
+  st_gc(tbl + 40, ge_cache(acc, d2));
+#pragma unroll 1
+  for (int i = 2; i < 8; ++i) {
+    acc = ge_add_cached(acc, c1);
+    st_gc(tbl + 40 * i, ge_cache(acc, d2));
+  }
+}
+
 }  // namespace
 
 // keys: [nkeys][24] words = x (clamped secret, 8 LE words), prefix (8), pk encoding (8);
@@ -615,50 +683,8 @@ extern "C" __global__ void __launch_bounds__(192) k_vrf_prove(const uint32_t* __
   for (int i = 0; i < 8; ++i) pk[i] = key[16 + i];
   const fe d = fe_const(C_D), d2 = fe_const(C_D2);
   // ---------------- phase 1: H = encode_to_curve_try_and_increment(pk, alpha), 12 counters at once
-  const int slot = w * 4 + q;
-  if (threadIdx.x < VP) s_win[threadIdx.x] = -1;
-  for (int base = 0; base < 256; base += VTRY) {
-    const int ctr = base + slot;
-    ge cand;
-    bool ok = false;
-    __syncthreads();
-    if (valid && s_win[p] < 0 && ctr < 256) {
-      Sha512 sh;
-      sha_init(sh);
-      sha_byte(sh, SUITE);
-      sha_byte(sh, 0x01);
-      sha_words(sh, pk, 8);
-      sha_bytes(sh, alpha, alpha_len);
-      sha_byte(sh, (uint8_t)ctr);
-      sha_byte(sh, 0x00);
-      uint8_t dig[64];
-      sha_final(sh, dig);
-      ok = ge_frombytes(cand, dig, d);
-    }
-    s_ok[slot][p] = ok ? 1 : 0;
-    __syncthreads();
-    if (ok && s_win[p] < 0) {
-      int first = slot;
-      for (int j = 0; j < slot; ++j)
-        if (s_ok[j][p]) { first = j; break; }
-      if (first == slot) {   // the smallest decoding counter of this proof: publish H
-        st_fe(&s_h[p][0], cand.X);
-        st_fe(&s_h[p][10], cand.Y);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < VP) {
-      int first = -1;
-      for (int j = 0; j < VTRY && first < 0; ++j)
-        if (s_ok[j][threadIdx.x]) first = j;
-      if (first >= 0 && s_win[threadIdx.x] < 0) s_win[threadIdx.x] = base + first;
-    }
-    __syncthreads();
-    const int pending = (threadIdx.x < VP && blockIdx.x * VP + threadIdx.x < n && s_win[threadIdx.x] < 0) ? 1 : 0;
-    if (!__syncthreads_or(pending)) break;
-  }
-  const bool have = valid && s_win[p] >= 0;   // probability 2^-256 of no valid counter: the host marks
-  //                                             an all-zero proof as failed
+  // probability 2^-256 of no valid counter: the host marks an all-zero proof as failed
+  const bool have = h2c_candidate(valid, pk, alpha, alpha_len, d, w * 4 + q, p, s_ok, s_win, s_h);
   ge H;
   if (have) {
     const fe hx = ld_fe(&s_h[p][0]), hy = ld_fe(&s_h[p][10]);
@@ -669,15 +695,7 @@ extern "C" __global__ void __launch_bounds__(192) k_vrf_prove(const uint32_t* __
   if (have && q == 0 && w <= 1) {
     H = ge_dbl(ge_dbl(ge_dbl(H, false), false), true);   // cofactor 8
     if (w == 0) {
-      const gc c1 = ge_cache(H, d2);
-      st_gc(tbl, c1);
-      ge acc = ge_dbl(H, true);
-      st_gc(tbl + 40, ge_cache(acc, d2));
-#pragma unroll 1
-      for (int i = 2; i < 8; ++i) {
-        acc = ge_add_cached(acc, c1);
-        st_gc(tbl + 40 * i, ge_cache(acc, d2));
-      }
+      ge_table(tbl, H, d2);
     } else {
       const fe hzi = fe_invert(H.Z);
       uint32_t hstr[8];
@@ -705,11 +723,11 @@ extern "C" __global__ void __launch_bounds__(192) k_vrf_prove(const uint32_t* __
   if (have && w == 0 && q == 0) {
     uint32_t x[8];
     for (int i = 0; i < 8; ++i) x[i] = key[i];
-    st_ge(&s_gamma[p][0], ge_mul_tbl(tbl, x));
+    st_ge(&s_gamma[p][0], ge_mul_tbl(tbl, x, 64));
   } else if (have && w == 1 && q == 0) {
     uint32_t k[8];
     for (int i = 0; i < 8; ++i) k[i] = s_k[p][i];
-    st_ge(&s_v[p][0], ge_mul_tbl(tbl, k));
+    st_ge(&s_v[p][0], ge_mul_tbl(tbl, k, 64));
   } else if (have && w == 2) {
     uint32_t k[8];
     for (int i = 0; i < 8; ++i) k[i] = s_k[p][i];
@@ -828,4 +846,177 @@ extern "C" int bsc_vrf_prove(const uint32_t* keys, const int* key_idx, const uin
                              int alpha_len, int n, const uint32_t* btab, uint32_t* scratch, uint8_t* pi, uint8_t* beta,
                              void* stream) {
   return bsc_vrf_prove_p(keys, key_idx, alphas, alpha_idx, alpha_len, n, btab, scratch, pi, beta, 0, stream);
+}
+
+// ---------------------------------------------------------------- the verifier (the opt-in audit, --vrf-audit)
+// One status per proof, the checks in the order of runtime/vrf.cpp::vrf_verify (the first failing one decides):
+//   0 valid | 1 the public key does not decode | 2 Gamma does not decode | 3 s >= L
+//   4 the challenge recomputed from H, Gamma, U = s B - c Y, V = s H - c Gamma differs from pi[32:48]
+//   5 valid, an expected output was supplied (expect_idx >= 0) and proof_to_hash(pi) differs from it
+// beta (may be null): the output for status 0 and 5, 64 zero bytes otherwise.  counter (may be null): incremented
+// once per proof whose status is not 0.
+// pks: public keys, 8 words at pks + pk_idx[i] * pk_stride (nothing else of a row is read: the prover's key
+// table is passed as keys + 16 with stride 24); scratch: [n][960] words, the tables of 8 H, Gamma and Y.
+// The prover's shape: 16 proofs per workgroup, 3 waves, wave-uniform roles, results handed over in LDS.
+//   phase 1  hash to curve on all three waves (h2c_candidate, shared with the prover)
+//   phase 2  wave 0: cofactor, the table of 8 H, s H (64 windows)
+//            wave 1: sub-lane 0 decodes Gamma, sub-lane 1 Y (the same code side by side), each builds its table
+//                    and multiplies by c (33 digits); sub-lane 0 then hashes 8 Gamma to the output
+//            wave 2: s B over the fixed-base table, 4 lanes per proof
+//   phase 3  wave 0: U, V, the encodings of 8 H, U, V with one inversion, the challenge, the status
+// A proof that fails a check stops working but its lanes walk every barrier; no thread returns before the last.
+extern "C" __global__ void __launch_bounds__(192) k_vrf_verify(
+    const uint32_t* __restrict__ pks, int pk_stride, const int* __restrict__ pk_idx, const uint8_t* __restrict__ alphas,
+    const int* __restrict__ alpha_idx, int alpha_len, int n, const uint32_t* __restrict__ btab, uint32_t* scratch,
+    const uint8_t* __restrict__ pi, const uint8_t* __restrict__ expect, const int* __restrict__ expect_idx,
+    int* __restrict__ status, uint8_t* __restrict__ beta, int* counter, int urgent) {
+  if (urgent) BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  __shared__ int s_ok[VTRY][VP];
+  __shared__ int s_win[VP];
+  __shared__ uint32_t s_h[VP][20];
+  __shared__ uint32_t s_h8[VP][40];      // 8 H (wave 0)
+  __shared__ uint32_t s_sh[VP][40];      // s H (wave 0)
+  __shared__ uint32_t s_cp[2][VP][40];   // c Gamma, c Y (wave 1, sub-lanes 0 and 1)
+  __shared__ int s_dec[2][VP];           // Gamma, Y decoded
+  __shared__ uint32_t s_u[4][VP][40];    // s B partial sums over 16 windows each (wave 2)
+  __shared__ uint8_t s_beta[VP][64];     // proof_to_hash (wave 1)
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int p = l & 15, q = l >> 4;
+  const int t = blockIdx.x * VP + p;
+  const bool valid = t < n;
+  const int tt = valid ? t : 0;
+  const uint32_t* key = pks + (long long)pk_idx[tt] * pk_stride;
+  const uint8_t* alpha = alphas + (long long)alpha_idx[tt] * alpha_len;
+  const uint8_t* proof = pi + (long long)tt * 80;
+  uint32_t pk[8], sw[8];
+  for (int i = 0; i < 8; ++i) {
+    pk[i] = key[i];
+    sw[i] = le_word(proof + 48, i);
+  }
+  bool s_lt = false;   // s < L (equal: not)
+  for (int i = 3; i >= 0; --i) {
+    const unsigned long long v = ((unsigned long long)sw[2 * i + 1] << 32) | sw[2 * i];
+    if (v != C_L[i]) {
+      s_lt = v < C_L[i];
+      break;
+    }
+  }
+  const bool act = valid && s_lt;
+  const fe d = fe_const(C_D), d2 = fe_const(C_D2);
+  // ---------------- phase 1
+  const bool have = h2c_candidate(act, pk, alpha, alpha_len, d, w * 4 + q, p, s_ok, s_win, s_h);
+  uint32_t* tbl = scratch + (long long)tt * 960;
+  // ---------------- phase 2
+  if (w == 0) {
+    if (have && q == 0) {
+      const fe hx = ld_fe(&s_h[p][0]), hy = ld_fe(&s_h[p][10]);
+      ge H = ge{hx, hy, fe_small(1), fe_mul(hx, hy)};
+      H = ge_dbl(ge_dbl(ge_dbl(H, false), false), true);   // cofactor 8
+      st_ge(&s_h8[p][0], H);
+      ge_table(tbl, H, d2);
+      st_ge(&s_sh[p][0], ge_mul_tbl(tbl, sw, 64));
+    }
+  } else if (w == 1) {
+    if (valid && q < 2) {
+      uint8_t enc[32];
+      for (int i = 0; i < 32; ++i) enc[i] = q == 0 ? proof[i] : (uint8_t)(pk[i >> 2] >> (8 * (i & 3)));
+      ge P;
+      const bool ok = ge_frombytes(P, enc, d);
+      s_dec[q][p] = ok ? 1 : 0;
+      if (ok && have) {
+        uint32_t* tb = tbl + 320 * (1 + q);
+        ge_table(tb, P, d2);
+        uint32_t cw[8];
+        for (int i = 0; i < 8; ++i) cw[i] = i < 4 ? le_word(proof + 32, i) : 0u;
+        st_ge(&s_cp[q][p][0], ge_mul_tbl(tb, cw, 33));
+        if (q == 0) {   // beta = SHA512(suite || 0x03 || encode(8 Gamma) || 0x00)
+          const ge G8 = ge_dbl(ge_dbl(ge_dbl(P, false), false), true);
+          const fe zi = fe_invert(G8.Z);
+          uint32_t e8[8];
+          enc_affine(e8, fe_mul(G8.X, zi), fe_mul(G8.Y, zi));
+          Sha512 sh;
+          sha_init(sh);
+          sha_byte(sh, SUITE);
+          sha_byte(sh, 0x03);
+          sha_words(sh, e8, 8);
+          sha_byte(sh, 0x00);
+          sha_final(sh, &s_beta[p][0]);
+        }
+      }
+    }
+  } else if (have) {
+    int8_t e[64];
+    signed_digits(e, sw);
+    ge r = ge_identity();
+#pragma unroll 1
+    for (int wi = 16 * q; wi < 16 * q + 16; ++wi) {
+      const int dg = e[wi];
+      if (dg > 0) r = ge_add_cached(r, ld_btab(btab, wi * 8 + dg - 1));
+      else if (dg < 0) r = ge_add_cached(r, gc_neg(ld_btab(btab, wi * 8 - dg - 1)));
+    }
+    st_ge(&s_u[q][p][0], r);
+  }
+  __syncthreads();
+  // ---------------- phase 3: the challenge and the status (wave 0, one lane per proof)
+  if (!(valid && w == 0 && q == 0)) return;
+  int st = !s_dec[1][p] ? 1 : !s_dec[0][p] ? 2 : !s_lt ? 3 : !have ? 4 : 0;
+  if (st == 0) {
+    const ge H8 = ld_ge(&s_h8[p][0]);
+    ge U = ld_ge(&s_u[0][p][0]);
+#pragma unroll 1
+    for (int j = 1; j < 4; ++j) U = ge_add_cached(U, ge_cache(ld_ge(&s_u[j][p][0]), d2));
+    U = ge_add_cached(U, gc_neg(ge_cache(ld_ge(&s_cp[1][p][0]), d2)));                           // s B - c Y
+    const ge V = ge_add_cached(ld_ge(&s_sh[p][0]), gc_neg(ge_cache(ld_ge(&s_cp[0][p][0]), d2)));   // s H - c Gamma
+    const fe zhu = fe_mul(H8.Z, U.Z);
+    const fe inv = fe_invert(fe_mul(zhu, V.Z));
+    const fe ziV = fe_mul(inv, zhu);
+    const fe inv2 = fe_mul(inv, V.Z);          // 1 / (Zh Zu)
+    const fe ziU = fe_mul(inv2, H8.Z);
+    const fe ziH = fe_mul(inv2, U.Z);
+    uint32_t eh[8], eu[8], ev[8];
+    enc_affine(eh, fe_mul(H8.X, ziH), fe_mul(H8.Y, ziH));
+    enc_affine(eu, fe_mul(U.X, ziU), fe_mul(U.Y, ziU));
+    enc_affine(ev, fe_mul(V.X, ziV), fe_mul(V.Y, ziV));
+    uint8_t cdig[64];
+    Sha512 sh;
+    sha_init(sh);
+    sha_byte(sh, SUITE);
+    sha_byte(sh, 0x02);
+    sha_words(sh, pk, 8);
+    sha_words(sh, eh, 8);
+    sha_bytes(sh, proof, 32);
+    sha_words(sh, eu, 8);
+    sha_words(sh, ev, 8);
+    sha_byte(sh, 0x00);
+    sha_final(sh, cdig);
+    int diff = 0;
+    for (int i = 0; i < 16; ++i) diff |= cdig[i] ^ proof[32 + i];
+    if (diff) st = 4;
+  }
+  if (st == 0 && expect != nullptr && expect_idx[t] >= 0) {
+    const uint8_t* ex = expect + (long long)expect_idx[t] * 64;
+    int diff = 0;
+    for (int i = 0; i < 64; ++i) diff |= ex[i] ^ s_beta[p][i];
+    if (diff) st = 5;
+  }
+  if (beta != nullptr) {
+    const bool out = st == 0 || st == 5;
+    uint8_t* o = beta + (long long)t * 64;
+    for (int i = 0; i < 64; ++i) o[i] = out ? s_beta[p][i] : (uint8_t)0;
+  }
+  status[t] = st;
+  if (st != 0 && counter != nullptr) atomicAdd(counter, 1);
+}
+
+// urgent: as in bsc_vrf_prove_p.  expect / expect_idx, beta and counter may be null.
+extern "C" int bsc_vrf_verify(const uint32_t* pks, int pk_stride, const int* pk_idx, const uint8_t* alphas,
+                              const int* alpha_idx, int alpha_len, int n, const uint32_t* btab, uint32_t* scratch,
+                              const uint8_t* pi, const uint8_t* expect, const int* expect_idx, int* status,
+                              uint8_t* beta, int* counter, int urgent, void* stream) {
+  if (n <= 0) return 0;
+  if (alpha_len < 0 || alpha_len > 1024) return -1;
+  hipLaunchKernelGGL(k_vrf_verify, dim3((n + VP - 1) / VP), dim3(192), 0, (hipStream_t)stream, pks, pk_stride, pk_idx,
+                     alphas, alpha_idx, alpha_len, n, btab, scratch, pi, expect, expect_idx, status, beta, counter,
+                     urgent);
+  return (int)hipGetLastError();
 }

@@ -855,8 +855,15 @@ PYBIND11_MODULE(_biscotti_rt, m) {
     return py::make_tuple(P(r.first), P(r.second));
   });
   m.def("vrf_verify", [](py::bytes pk, py::bytes alpha, py::bytes pi) -> py::object {
+    // without the GIL: the VRF audit verifies a round's host proofs from several Python threads
+    const Bytes k = B(pk), a = B(alpha), p = B(pi);
     Bytes beta;
-    if (!vrf_verify(B(pk), B(alpha), B(pi), &beta)) return py::none();
+    bool ok;
+    {
+      py::gil_scoped_release rel;
+      ok = vrf_verify(k, a, p, &beta);
+    }
+    if (!ok) return py::none();
     return P(beta);
   });
   m.def("vrf_prove_batch", [](std::vector<py::bytes> seeds, py::bytes alpha, int threads) {

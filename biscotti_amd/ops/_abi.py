@@ -40,6 +40,7 @@ SIGNATURES = {
     # vrf.hip
     "bsc_vrf_prove": [P, P, P, P, I, I, P, P, P, P, P],
     "bsc_vrf_prove_p": [P, P, P, P, I, I, P, P, P, P, I, P],
+    "bsc_vrf_verify": [P, I, P, P, P, I, I, P, P, P, P, P, P, P, P, I, P],
     # kzg.hip
     "bsc_kzg_blocks": [I, I],
     "bsc_kzg_rlc": [P, P, P, P, I, I, I, P, I, I, U64, P, P, P],

@@ -14,7 +14,6 @@ class RunConfig:
     dataset: str = "mnist"          # -d  mnist | creditcard
     peers_file: str | None = None   # -f
     my_ip: str = ""                 # -a
-    my_private_ip: str = ""         # -pa
     port: str = ""                  # -p
     colluders: int = 0              # -c  percent
     num_miners: int = 3             # -na
@@ -74,9 +73,15 @@ class RunConfig:
     audit_aggregate: bool = True    # check the recovered aggregate against the miners' summed chunk
     #                                 commitments (verifyCommitment on the aggregate; not in the reference)
     comm_timeout_s: float = 300.0   # collective timeout: a dead rank fails the job instead of hanging it
-    vrf_device: bool = True         # GPU: the VRF proofs nothing reads (roles proof Q7, the noiser proofs)
-    #                                 run on the device (kernels/vrf.hip); the host computes only the
+    vrf_device: bool = True         # GPU: the VRF proofs the reference never reads (roles proof Q7, the noiser
+    #                                 proofs) run on the device (kernels/vrf.hip); the host computes only the
     #                                 64-byte outputs the lottery consumes
+    vrf_audit: bool = False         # verify every VRF proof this rank produces (not in the reference): device
+    #                                 batches in place by k_vrf_verify right behind the prover, at the batch's
+    #                                 priority, the noiser proofs also against the output the lottery consumed
+    #                                 (status 5); host proofs (the run's last round, --no-vrf-device, no GPU)
+    #                                 with the host verifier.  drain() sets stats vrf_audit_checked /
+    #                                 vrf_audit_failures; failures are logged once, never change the chain
     kzg_audit: str = "off"          # batched verifySecret (kyber.go:650-673) over every (chunk, share point) of
     #                                 the aggregate: off | consistent (y against PK[poly*k]) | literal (y
     #                                 against G1: the reference's formula, which only chunk 0 satisfies, Q9).
@@ -260,7 +265,7 @@ def add_reference_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("-d", dest="dataset", default="mnist", help="dataset (mnist | creditcard)")
     ap.add_argument("-f", dest="peers_file", default=None, help="peers file (IP:port per line)")
     ap.add_argument("-a", dest="my_ip", default="", help="public IP")
-    ap.add_argument("-pa", dest="my_private_ip", default="", help="private IP")
+    ap.add_argument("-pa", dest="my_private_ip", default="", help="private IP (accepted, never read: no field)")
     ap.add_argument("-p", dest="port", default="", help="port")
     ap.add_argument("-c", dest="colluders", type=int, default=0, help="colluders (percent)")
     ap.add_argument("-na", dest="num_miners", type=int, default=3, help="number of aggregators")
@@ -307,6 +312,9 @@ def add_framework_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--no-audit-aggregate", dest="audit_aggregate", action="store_false")
     ap.add_argument("--no-vrf-device", dest="vrf_device", action="store_false",
                     help="compute every VRF proof on host threads")
+    ap.add_argument("--vrf-audit", dest="vrf_audit", action="store_true",
+                    help="verify every VRF proof this rank produces (device batches in place, K16); failures "
+                         "are counted and logged, never change the chain")
     ap.add_argument("--kzg-audit", default="off", choices=["off", "consistent", "literal"],
                     help="batched verifySecret over each round's aggregate (K13)")
     ap.add_argument("--comm-timeout", dest="comm_timeout_s", type=float, default=300.0)

@@ -47,6 +47,7 @@ from .head import PlanView, RoundHeadMixin
 from .kzg_audit import KzgAuditMixin
 from .secagg import SecAggMixin
 from .verify import VerifyMixin
+from .vrf_audit import VrfAuditMixin
 
 SIDE_STREAM_SKIP_EVERY = 4   # the speculative-MSM stream leaves every 4th CU to the critical path
 VRF_BATCH_ROUNDS = 16        # device VRF proofs: rounds per prover launch
@@ -74,7 +75,7 @@ class RoundResult:
     approved_by_krum: list = field(default_factory=list)  # updates at least one verifier accepted
 
 
-class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, FaultsMixin):
+class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, VrfAuditMixin, FaultsMixin):
     def __init__(self, cfg: RunConfig, comm: Comm | None = None):
         cfg.validate()
         self.cfg = cfg
@@ -207,6 +208,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Fa
             # registers per wave) and slows the MSM waves that share them; per-round launches round-robin over
             # several streams cut the end-of-run drain but cost ~0.07 ms in every round (docs/PERF.md round 3)
             self.vrf_dev = DeviceVrfProver(self.dev, VRF_BATCH_ROUNDS)
+            if cfg.vrf_audit:
+                self.vrf_dev.audit = True   # every batch is verified in place behind its prove launch (vrf_audit.py)
         self._agg_idx: dict = {}      # (contributing, parts) -> resident aggregation index tensors
         self._W_next = None          # device copy of the model a block under construction carries
         self._pre = None             # next round's local step + commitments, queued behind the recovery
@@ -222,6 +225,7 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Fa
         self.stats = {"unmasked_updates": 0, "total_updates": 0, "audit_failures": 0, "vrf_outputs": 0,
                       "native_collectives": int(self._native_comm)}
         self._kzg_init(cfg)
+        self._vrf_audit_init(cfg)
         self._churn = {"down": {}, "view": {}, "epoch": {}, "acc": 0.0, "kills": 0, "rejoins": 0,
                        "synced_blocks": 0}
         self.stats["churn"] = self._churn
@@ -300,7 +304,10 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Fa
                                [self.vrf_roles_seed[p] for p in self.local])
             # one proof now: the prover kernel's code object is loaded at its first launch (several ms)
             with S.use(self.vrf_stream):
-                self.vrf_dev.prove([self.vrf_noise_seed[self.lo]], [bytes(self.vrf_dev.ALPHA_LEN)])
+                pi, _ = self.vrf_dev.prove([self.vrf_noise_seed[self.lo]], [bytes(self.vrf_dev.ALPHA_LEN)])
+                if cfg.vrf_audit:   # and the verifier kernel's
+                    self.vrf_dev.verify([self.R.vrf_key_material(self.vrf_noise_seed[self.lo])[64:]],
+                                        [bytes(self.vrf_dev.ALPHA_LEN)], [bytes(pi.cpu().numpy())])
             # the batched launches' buffers: noiser + roles proofs of every local peer per round
             self.vrf_dev.reserve(self.vrf_stream, self.vrf_dev.batch_rounds * 2 * len(self.local))
             torch.cuda.synchronize(self.dev)
@@ -339,6 +346,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Fa
             hp, self._host_proofs = self._host_proofs, []
             for j in hp:
                 j.wait()
+            if self.cfg.vrf_audit:
+                self._vrf_audit_finish()
             t2 = time.perf_counter()
             joins, self._sign_joins = self._sign_joins, []
             for join in joins:
@@ -560,6 +569,13 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Fa
             # joined one round later (drain() joins the last ones), so the round does not wait for them
             self.drain(final=False)
             self._pending_roles = (head["fut_noise"], head["fut_roles"])
+            if head.get("vrf_audit_host") is not None:
+                # the host path's audit: this round's noiser and roles proofs come with the jobs above
+                h, nseeds, roles, rseeds = head["vrf_audit_host"]
+                self._vrf_audit_host_job(head["fut_noise"], nseeds, head.get("vrf_index"), h,
+                                         self._vrf_audit_expect(head, local_workers), it, local_workers)
+                self._vrf_audit_host_job(head["fut_roles"], rseeds, None, h, None, it, roles)
+                self._vrf_audit_poll(final=False)
         self.stats["total_updates"] += n_up
         if n_up:
             self._note_block_depth(head, self._last_nodes)
@@ -635,8 +651,15 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Fa
                         self._host_proofs.append(self.R.vrf_proofs_async(seeds, h,
                                                                          max(1, min(8, cfg.host_threads - 2))))
                         self.stats["vrf_host_proofs"] = self.stats.get("vrf_host_proofs", 0) + len(seeds)
+                        if cfg.vrf_audit:   # checked by the host verifier when drain() joins the job
+                            ex = self._vrf_audit_expect(head, lw)
+                            self._vrf_audit_host_job(self._host_proofs[-1], seeds, None, h,
+                                                     ex + [None] * (len(seeds) - len(ex)), it,
+                                                     list(lw) + [p for p in self.local if lv[p]])
                 else:
-                    self.vrf_dev.submit(self._vrf_key_rows(lw, lv), h, self.vrf_stream)
+                    # (the audit adds what its verify launch needs: which batches launch, and when, stays)
+                    self.vrf_dev.submit(self._vrf_key_rows(lw, lv), h, self.vrf_stream,
+                                        **(self._vrf_audit_args(head, lw, lv, it) if cfg.vrf_audit else {}))
                     if remaining == 2:   # the penultimate round: its launch (~2.2 ms) ends with the last round
                         self.vrf_dev.flush(self.vrf_stream)
             self._resolve_evals(wait=len(self._evals) > 3)   # a bounded backlog: the host rings hold 4

@@ -94,6 +94,12 @@ class RoundHeadMixin:
                 if roles:
                     fut_roles = R.vrf_prove_batch_async(roles, latest_hash, 8, fut_noise)
         head.update(fut_noise=fut_noise, fut_roles=fut_roles)
+        if cfg.vrf_audit and not dev:
+            # the host path's audit (vrf_audit.py) verifies these jobs' proofs once the round has run: the message
+            # and the keys as they are now (the block's commit moves the hash, a churn restart the keys)
+            head["vrf_audit_host"] = (bytes(latest_hash), [self.vrf_noise_seed[w] for w in local_workers],
+                                      [p for p in self.local if live[p]],
+                                      [self.vrf_roles_seed[p] for p in self.local if live[p]])
         tm, it = self.timer, plan.iteration
         # the local step (and the commitments) may already be in flight: the native pre-step queued behind the
         # recovery of the model this head starts from, for every local peer.  The decision is the same on every

@@ -27,6 +27,12 @@ int bsc_segment_sum_h(const uint32_t* pts, int ngroups, int n, int stride, int o
                       void* stream);
 int bsc_chunk_check_h(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
                       const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream);
+int bsc_g1_unmarshal(const uint8_t* in, int n, const int* pre, uint32_t* out, int* valid, void* stream);
+int bsc_chain_audit(const double* models, const int* kind, const int* offsets, int L, int d, const double* plain,
+                    const int* pbeg, const int* pend, int np, const uint8_t* commits, const int* len_ok, int n,
+                    const uint32_t* tbl_pk, int B0, int NW, double scale, double tol, double wmax, int slab,
+                    long long* coeffs, const int* rows, uint32_t* partial, uint32_t* msm, uint32_t* aff, int* valid,
+                    int* res, int* h_res, void* stream);
 int bsc_wave_prio_msm(int on);
 // ml.hip
 int bsc_softmax_step_ones(const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,

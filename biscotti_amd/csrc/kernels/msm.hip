@@ -19,6 +19,7 @@
 //    pulled into a single XCD's L2.
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "bn256_dev.h"
@@ -639,6 +640,164 @@ extern "C" __global__ void __launch_bounds__(64) k_to_affine(const uint32_t* pts
   st_aff(out + 16 * (size_t)i, jac_to_aff(ld_jac(pts + 24 * (size_t)i)));
 }
 
+// ------------------------------------------------------------------ chain audit
+// Each block of a chain against the commitments it stores (protocol/chain_audit.py): the model step
+// W_b - W_{b-1}, as integer coefficients c, must commit to the G1 sum of the block's update commitments,
+//   sum_i c_i PK[i] == sum_u C_u.
+// Three kernels around the existing row MSM (k_commit_rows, rows = blocks): the coefficient rows from the
+// stacked models, the inverse of k_marshal, and a per-row segment sum + projective comparison.
+// Status codes (the same numbers as chain_audit.py): a larger code wins, so the guards combine with atomicMax.
+#define AUD_OK 0
+#define AUD_EMPTY 1
+#define AUD_NO_COMMITMENTS 2
+#define AUD_EMPTY_CHANGED 3
+#define AUD_MISMATCH 4
+#define AUD_BAD_POINT 5
+#define AUD_INEXACT 6
+#define AUD_RANGE 7
+#define AUD_KIND_EMPTY 0
+#define AUD_KIND_SECAGG 1
+
+// Coefficient rows.  mode 0, row r = block r of the slab, a = models fp64 [nrows + 1][d], kind[r]:
+//   SECAGG  c_i = rint((a[r+1][i] - a[r][i]) * scale)
+//   EMPTY   the two models must agree bit for bit (EMPTY_CHANGED otherwise); c = 0
+//   other   c = 0 (the row MSM then has no work for it)
+// mode 1, row r = one update of a plain block, a = its delta fp64 [nrows][d]: c_i = trunc(a[r][i] * scale), the
+// engine's quantize (ml.hip); a value that is not finite or leaves int64 (|v * scale| >= 2^62) is RANGE.
+//
+// The guards of mode 0, with u = 2^-53, M = max(|W|, |W'|) over the two models and delta = v / scale for the
+// integer aggregate v the engine applied as W' = fl(W + fl(v / scale)) (ml.hip k_recover*):
+//   fl(v / scale) = delta (1 + e1), W' = (W + delta (1 + e1))(1 + e2)  =>  |W' - W - delta| <= u |delta| + u |W'|
+//   x = fl(W' - W) = (W' - W)(1 + e3), y = fl(x * scale) = x scale (1 + e4)   (|e_k| <= u)
+//   |y - v| <= scale u (|delta| + |W'| + 2 |W' - W|) (1 + O(u)) <= scale u (2M + M + 4M) = 7 u M scale,
+// since |delta| <= |W' - W| + u(|delta| + |W'|) and |W' - W| <= 2M.  With wmax = 2^40 / scale every model
+// within |W| <= wmax gives |y - v| < 7 * 2^-53 * 2^40 = 2^-10.19 quanta: under tol = 2^-10, so a chain the
+// engine produced can never be INEXACT inside RANGE, and rint(y) = v.  Half a quantum (residual 0.5) is far
+// above tol.  |y| <= 2 * 2^40, so the conversion to int64 is exact.  (scale = 10^4: wmax ~ 1.1e8 > 2^26.)
+// Bandwidth-bound: one lane per coefficient, coalesced along d; vector stores only.
+extern "C" __global__ void __launch_bounds__(256) k_chain_coeffs(const double* a, int nrows, int d, const int* kind,
+                                                                int mode, double scale, double tol, double wmax,
+                                                                long long* coeffs, int* status) {
+  const int r = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (r >= nrows || i >= d) return;
+  long long c = 0;
+  int st = 0;
+  if (mode == 1) {
+    const double y = a[(size_t)r * d + i] * scale;
+    if (fabs(y) < 4611686018427387904.0) c = (long long)y;   // false for NaN
+    else st = AUD_RANGE;
+  } else {
+    const int k = kind[r];
+    const double w0 = a[(size_t)r * d + i], w1 = a[(size_t)(r + 1) * d + i];
+    if (k == AUD_KIND_SECAGG) {
+      if (!(fabs(w0) <= wmax) || !(fabs(w1) <= wmax)) {
+        st = AUD_RANGE;
+      } else {
+        const double y = (w1 - w0) * scale, ry = rint(y);
+        if (fabs(y - ry) > tol) st = AUD_INEXACT;
+        else c = (long long)ry;
+      }
+    } else if (k == AUD_KIND_EMPTY) {
+      if (__double_as_longlong(w0) != __double_as_longlong(w1)) st = AUD_EMPTY_CHANGED;
+    }
+  }
+  coeffs[(size_t)r * d + i] = c;
+  if (st != 0) atomicMax(&status[r], st);
+}
+
+// kyber marshal (64 B: big-endian x || y; zeros = infinity) -> affine Montgomery [n][16] + validity, the
+// inverse of k_marshal.  Valid: infinity, or x, y < p with y^2 = x^3 + 3.  An invalid point is written as
+// infinity.  pre (nullable): a point whose flag is 0 there is invalid whatever its bytes (a commitment that
+// was not 64 bytes long).  One lane per point.
+extern "C" __global__ void __launch_bounds__(64) k_g1_unmarshal(const uint8_t* in, int n, const int* pre,
+                                                               uint32_t* out, int* valid) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t R2[8] = {0x7e444f56u, 0x9c21c3ffu, 0xb2efb0c2u, 0x409ed151u,
+                          0x80fb1651u, 0x0c6dc37bu, 0x2c2380b7u, 0x7c36e0e6u};   // R^2 mod p
+  const uint8_t* s = in + 64 * (size_t)i;
+  fp x, y, r2;
+  uint32_t any = 0;
+#pragma unroll
+  for (int l = 0; l < 8; ++l) {
+    const uint8_t* bx = s + 4 * (7 - l);
+    const uint8_t* by = s + 32 + 4 * (7 - l);
+    x.v[l] = ((uint32_t)bx[0] << 24) | ((uint32_t)bx[1] << 16) | ((uint32_t)bx[2] << 8) | (uint32_t)bx[3];
+    y.v[l] = ((uint32_t)by[0] << 24) | ((uint32_t)by[1] << 16) | ((uint32_t)by[2] << 8) | (uint32_t)by[3];
+    any |= x.v[l] | y.v[l];
+    r2.v[l] = R2[l];
+  }
+  // a < p, from the top limb down
+  bool xlt = false, ylt = false, xdec = false, ydec = false;
+#pragma unroll
+  for (int l = 7; l >= 0; --l) {
+    if (!xdec && x.v[l] != P[l]) { xlt = x.v[l] < P[l]; xdec = true; }
+    if (!ydec && y.v[l] != P[l]) { ylt = y.v[l] < P[l]; ydec = true; }
+  }
+  aff q;
+  q.x = fp_zero();
+  q.y = fp_zero();
+  int ok = (pre == nullptr || pre[i] != 0) ? 1 : 0;
+  if (ok && any != 0) {
+    ok = 0;
+    if (xlt && ylt) {
+      const fp mx = fp_mul(x, r2), my = fp_mul(y, r2);
+      const fp one = fp_one();
+      const fp three = fp_add(fp_add(one, one), one);
+      if (fp_eq(fp_sqr(my), fp_add(fp_mul(fp_sqr(mx), mx), three))) {
+        ok = 1;
+        q.x = mx;
+        q.y = my;
+      }
+    }
+  }
+  st_aff(out + 16 * (size_t)i, q);
+  valid[i] = ok;
+}
+
+// One wave per row (a block, or one update of a plain block): the row's points [beg[r], end[r]) of `pts`
+// (affine, k_g1_unmarshal) are summed -- lane t takes points t, t + 64, ... with mixed additions, then an LDS
+// tree over the lanes that hold a partial sum (k_segment_sum's form) -- and lane 0 compares the sum
+// projectively (jac_equal: no inversion) with the row's commitment msm[r] from the row MSM.
+// A row whose status is not OK on entry (a guard of k_chain_coeffs fired, or nothing to check) is skipped,
+// uniformly for the wave.  An invalid point ends the row as BAD_POINT with the smallest such index (relative
+// to beg[r]) in first[r]; otherwise OK or MISMATCH.  LDS: 64 x 96 B = 6 KB.
+extern "C" __global__ void __launch_bounds__(64) k_block_commit_check(const uint32_t* pts, const int* valid,
+                                                                     const int* beg, const int* end,
+                                                                     const uint32_t* msm, int nrows, int* status,
+                                                                     int* first) {
+  __shared__ uint32_t sh[64 * 24];
+  __shared__ int bad;
+  const int r = xcd_remap(blockIdx.x, gridDim.x), t = threadIdx.x;
+  if (r >= nrows) return;
+  if (status[r] != AUD_OK) return;   // uniform per wave
+  const int b0 = beg[r], n = end[r] - b0;
+  if (t == 0) bad = 0x7FFFFFFF;
+  __syncthreads();
+  jac acc = jac_inf();
+  for (int k = t; k < n; k += 64) {
+    if (valid[b0 + k] == 0) atomicMin(&bad, k);
+    else acc = jac_add_aff(acc, ld_aff(pts + 16 * (size_t)(b0 + k)));
+  }
+  st_jac(sh + t * 24, acc);
+  __syncthreads();
+  int top = 1;
+  while (top < n && top < 64) top <<= 1;
+  for (int s = top / 2; s > 0; s >>= 1) {
+    if (t < s) st_jac(sh + t * 24, jac_add(ld_jac(sh + t * 24), ld_jac(sh + (t + s) * 24)));
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (bad != 0x7FFFFFFF) {
+      status[r] = AUD_BAD_POINT;
+      first[r] = bad;
+    } else if (!jac_equal(ld_jac(sh), ld_jac(msm + 24 * (size_t)r))) {
+      status[r] = AUD_MISMATCH;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ C ABI launchers
 // (same translation unit as the kernels: no relocatable device code needed)
 static inline int blocks_for(long long n, int bs) { return (int)((n + bs - 1) / bs); }
@@ -859,6 +1018,66 @@ extern "C" int bsc_to_affine(const uint32_t* pts, int n, uint32_t* out, void* st
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_to_affine, dim3(blocks_for(n, 64)), dim3(64), 0, (hipStream_t)stream, pts, n, out);
   return (int)hipGetLastError();
+}
+
+// pre (nullable): int32 [n], 0 = invalid whatever the bytes; out: affine [n][16]; valid: int32 [n]
+extern "C" int bsc_g1_unmarshal(const uint8_t* in, int n, const int* pre, uint32_t* out, int* valid, void* stream) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_g1_unmarshal, dim3(blocks_for(n, 64)), dim3(64), 0, (hipStream_t)stream, in, n, pre, out,
+                     valid);
+  return (int)hipGetLastError();
+}
+
+// The chain audit of L blocks (and the np updates of their plain blocks), all queued on `stream`:
+//   models fp64 [L + 1][d], kind int32 [L], offsets int32 [L + 1] (CSR into the n commitments);
+//   plain fp64 [np][d] update vectors with their commitment at pbeg[r] (pend[r] = pbeg[r] + 1);
+//   commits uint8 [n][64], len_ok int32 [n];
+//   res int32 [2 L + 2 np] = status [L] | first [L] | plain status [np] | plain first [np], pre-set by the
+//   caller (OK for rows to check, the final code for the others, first = -1), copied to h_res (pinned,
+//   nullable) at the end: the one read-back.
+// Rows are processed `slab` at a time through the scratch (coeffs int64 [slab][d], rows = 0..slab-1, partial
+// [slab * nslab][24], msm [slab][24]; aff [n][16], valid [n]).  The slab bounds the scratch, not the chain: the
+// default of 256 rows (ops/bn256.py) is 16 MB of coefficients at d = 7850 and 2048 blocks of the row MSM per
+// launch -- eight per CU, so the GPU is full and a longer slab would only buy memory.
+extern "C" int bsc_chain_audit(const double* models, const int* kind, const int* offsets, int L, int d,
+                               const double* plain, const int* pbeg, const int* pend, int np,
+                               const uint8_t* commits, const int* len_ok, int n, const uint32_t* tbl_pk, int B0,
+                               int NW, double scale, double tol, double wmax, int slab, long long* coeffs,
+                               const int* rows, uint32_t* partial, uint32_t* msm, uint32_t* aff, int* valid,
+                               int* res, int* h_res, void* stream) {
+  if (L < 0 || np < 0 || n < 0 || d <= 0 || slab < 1 || slab > 4096) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  int err = bsc_g1_unmarshal(commits, n, len_ok, aff, valid, stream);
+  if (err != 0) return err;
+  int* status = res;
+  int* first = res + L;
+  int* pstatus = res + 2 * (size_t)L;
+  int* pfirst = pstatus + np;
+  const int gx = blocks_for(d, 256);
+  for (int s0 = 0; s0 < L; s0 += slab) {
+    const int nb = std::min(slab, L - s0);
+    hipLaunchKernelGGL(k_chain_coeffs, dim3(gx, nb), dim3(256), 0, st, models + (size_t)s0 * d, nb, d, kind + s0, 0,
+                       scale, tol, wmax, coeffs, status + s0);
+    err = bsc_commit_rows(coeffs, d, rows, nb, tbl_pk, B0, NW, partial, msm, stream);
+    if (err != 0) return err;
+    hipLaunchKernelGGL(k_block_commit_check, dim3(nb), dim3(64), 0, st, aff, valid, offsets + s0, offsets + s0 + 1,
+                       msm, nb, status + s0, first + s0);
+  }
+  for (int s0 = 0; s0 < np; s0 += slab) {
+    const int nb = std::min(slab, np - s0);
+    hipLaunchKernelGGL(k_chain_coeffs, dim3(gx, nb), dim3(256), 0, st, plain + (size_t)s0 * d, nb, d,
+                       (const int*)nullptr, 1, scale, tol, wmax, coeffs, pstatus + s0);
+    err = bsc_commit_rows(coeffs, d, rows, nb, tbl_pk, B0, NW, partial, msm, stream);
+    if (err != 0) return err;
+    hipLaunchKernelGGL(k_block_commit_check, dim3(nb), dim3(64), 0, st, aff, valid, pbeg + s0, pend + s0, msm, nb,
+                       pstatus + s0, pfirst + s0);
+  }
+  err = (int)hipGetLastError();
+  if (err != 0) return err;
+  const size_t nres = 2 * (size_t)L + 2 * (size_t)np;
+  if (h_res != nullptr && nres > 0)
+    return (int)hipMemcpyAsync(h_res, res, nres * sizeof(int), hipMemcpyDeviceToHost, st);
+  return 0;
 }
 
 // ------------------------------------------------------------------ streams

@@ -506,6 +506,13 @@ PYBIND11_MODULE(_biscotti_rt, m) {
   m.def("g1_is_valid", [](py::bytes a) {
     try { G1::unmarshal(B(a)); return true; } catch (...) { return false; }
   });
+  m.def("g1_marshaled_valid", [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a) {
+    // [n, 64] marshals -> int32 [n]: 1 for infinity (zeros) or x, y < p on the curve (G1::marshaled_valid)
+    if (a.ndim() != 2 || a.shape(1) != 64) throw std::runtime_error("expected [n, 64] uint8");
+    py::array_t<int32_t> out(a.shape(0));
+    for (py::ssize_t i = 0; i < a.shape(0); ++i) out.mutable_data()[i] = G1::marshaled_valid(a.data(i, 0)) ? 1 : 0;
+    return out;
+  });
   m.def("g1_affine_mont_u32", [](py::bytes a) { return g1_affine_u32({G1::unmarshal(B(a))}); });
   m.def("g1_marshal_jac_u32", [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> jac) {
     // [n, 24] Montgomery Jacobian limbs (device layout) -> list of 64-byte marshals
@@ -1132,6 +1139,32 @@ PYBIND11_MODULE(_biscotti_rt, m) {
         }
         return py::make_tuple(ok, why);
       })
+      // the chain audit's inputs for blocks [from, to) as arrays (ledger.hpp AuditArrays; protocol/chain_audit.py)
+      .def("audit_arrays", [](const Blockchain& c, size_t d, size_t from, size_t to) {
+        AuditArrays a;
+        {
+          py::gil_scoped_release nogil;
+          a = c.audit_arrays(d, from, to);
+        }
+        const py::ssize_t L = py::ssize_t(a.kind.size()), n = py::ssize_t(a.flags.size());
+        const py::ssize_t np_ = py::ssize_t(a.plain_update.size()), dd = py::ssize_t(d);
+        py::array_t<double> models({L ? L + 1 : py::ssize_t(0), dd});
+        if (!a.models.empty()) std::memcpy(models.mutable_data(), a.models.data(), 8 * a.models.size());
+        py::array_t<uint8_t> commits({n, py::ssize_t(64)});
+        if (n) std::memcpy(commits.mutable_data(), a.commits.data(), a.commits.size());
+        py::array_t<double> pd({np_, dd});
+        if (!a.plain_delta.empty()) std::memcpy(pd.mutable_data(), a.plain_delta.data(), 8 * a.plain_delta.size());
+        py::dict out;
+        out["first"] = a.first;
+        out["models"] = models;
+        out["kind"] = py::array_t<int32_t>(L, a.kind.data());
+        out["offsets"] = py::array_t<int32_t>(py::ssize_t(a.offsets.size()), a.offsets.data());
+        out["commits"] = commits;
+        out["flags"] = py::array_t<int32_t>(n, a.flags.data());
+        out["plain_update"] = py::array_t<int32_t>(np_, a.plain_update.data());
+        out["plain_delta"] = pd;
+        return out;
+      }, py::arg("d"), py::arg("first") = 1, py::arg("last") = size_t(-1))
       .def("print_chain", &Blockchain::print_chain)
       .def("truncate", [](Blockchain& c, size_t n) { if (n < c.blocks.size()) c.blocks.resize(n); });
   m.def("gob_uint", [](uint64_t x) { Bytes b; gob_put_uint(b, x); return P(b); });

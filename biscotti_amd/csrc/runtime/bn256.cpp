@@ -401,6 +401,18 @@ G1 G1::unmarshal(const Bytes& b) {
   return p;
 }
 
+bool G1::marshaled_valid(const u8* p64) {
+  const U256 x = U256::from_be(p64), y = U256::from_be(p64 + 32);
+  if (x.is_zero() && y.is_zero()) return true;
+  if (cmp(x, PRIME()) >= 0 || cmp(y, PRIME()) >= 0) return false;
+  const MontField& F = Fp();
+  const U256 ax = F.to_mont(x), ay = F.to_mont(y);
+  U256 y2, x3;
+  F.sqr(y2, ay);
+  F.sqr(x3, ax); F.mul(x3, x3, ax); F.add(x3, x3, mont_small(3));
+  return y2 == x3;
+}
+
 bool G1::equals(const G1& o) const { return marshal() == o.marshal(); }
 
 G1GenTable::G1GenTable() {

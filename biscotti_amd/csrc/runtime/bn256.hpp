@@ -93,6 +93,9 @@ struct G1 {
   void to_affine(U256& ax, U256& ay) const;  // Montgomery affine; infinity -> (0, 0)
   Bytes marshal() const;              // 64 B, kyber format
   static G1 unmarshal(const Bytes& b);  // throws on malformed / not on curve
+  // strict form for audits (unmarshal reduces a coordinate >= p): 64 bytes that are all zero (infinity) or
+  // big-endian x || y with x, y < p on y^2 = x^3 + 3
+  static bool marshaled_valid(const u8* p64);
   bool on_curve() const;
   bool equals(const G1& o) const;
 };

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <limits>
 
 #include "bn256.hpp"
 #include "hash.hpp"
@@ -417,6 +418,68 @@ bool Blockchain::verify_range(size_t from, size_t to, std::string* why) const {
   }
   return true;
 }
+AuditArrays Blockchain::audit_arrays(size_t d, size_t from, size_t to) const {
+  if (from < 1) fail("ledger: audit_arrays starts at block 1");
+  to = std::min(to, blocks.size());
+  AuditArrays a;
+  a.d = d;
+  a.first = from;
+  if (to <= from) {
+    a.offsets.push_back(0);
+    return a;
+  }
+  const size_t L = to - from;
+  a.models.resize((L + 1) * d);
+  for (size_t k = 0; k <= L; ++k) {
+    const std::vector<double>& w = blocks[from - 1 + k].data.global_w;
+    double* row = a.models.data() + k * d;
+    if (w.size() == d) {
+      if (d) memcpy(row, w.data(), 8 * d);
+    } else {
+      std::fill(row, row + d, std::numeric_limits<double>::quiet_NaN());
+    }
+  }
+  a.kind.resize(L);
+  a.offsets.assign(L + 1, 0);
+  for (size_t k = 0; k < L; ++k) {
+    const std::vector<Update>& us = blocks[from + k].data.deltas;
+    bool any_commit = false, any_vec = false;
+    for (auto& u : us) {
+      any_commit = any_commit || !u.commitment.empty();
+      any_vec = any_vec || !u.delta.empty();
+    }
+    const int32_t kind = us.empty() ? AuditArrays::EMPTY
+                         : !any_commit ? AuditArrays::NONE
+                         : any_vec ? AuditArrays::PLAIN
+                                   : AuditArrays::SECAGG;
+    a.kind[k] = kind;
+    if (kind == AuditArrays::SECAGG || kind == AuditArrays::PLAIN) {
+      for (auto& u : us) {
+        int32_t f = u.accepted ? AuditArrays::ACCEPTED : 0;
+        const size_t o = a.commits.size();
+        a.commits.resize(o + 64, 0);
+        if (u.commitment.size() == 64) {
+          memcpy(a.commits.data() + o, u.commitment.data(), 64);
+          f |= AuditArrays::LEN_OK;
+        }
+        if (kind == AuditArrays::PLAIN) {
+          const size_t po = a.plain_delta.size();
+          a.plain_delta.resize(po + d, 0.0);
+          if (u.delta.size() == d) {
+            if (d) memcpy(a.plain_delta.data() + po, u.delta.data(), 8 * d);
+            f |= AuditArrays::VEC_OK;
+          }
+          a.plain_update.push_back(int32_t(a.flags.size()));
+        }
+        a.flags.push_back(f);
+      }
+    }
+    if (a.flags.size() > size_t(std::numeric_limits<int32_t>::max())) fail("ledger: audit_arrays: too many updates");
+    a.offsets[k + 1] = int32_t(a.flags.size());
+  }
+  return a;
+}
+
 std::string Blockchain::print_chain() const {
   std::string s;
   for (auto& b : blocks) {

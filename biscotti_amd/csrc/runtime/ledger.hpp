@@ -57,8 +57,31 @@ std::string go_format_float_slice(const std::vector<double>& v);  // arrayToStri
 std::string update_string(const Update& u);                        // Update.String()
 std::string blockdata_string(const BlockData& d);                  // BlockData.String()
 
+// The chain audit's inputs for blocks [from, to) as flat arrays (protocol/chain_audit.py): what each block's
+// model step and commitments are, without a Python object per update.
+//   kind of a block: EMPTY no deltas; SECAGG deltas with a commitment and no delta vector; PLAIN deltas that
+//   carry their vectors; NONE deltas without any commitment (FedSys chains).
+//   flags of an update: ACCEPTED; LEN_OK the commitment is 64 bytes (else its slot is zeros); VEC_OK (plain
+//   blocks) the delta vector has d entries (else its row is zeros).
+// A model whose length is not d is not one the key can commit to: its row is filled with NaN, which the audit
+// reports as RANGE.
+struct AuditArrays {
+  enum Kind : int32_t { EMPTY = 0, SECAGG = 1, PLAIN = 2, NONE = 3 };
+  enum Flag : int32_t { ACCEPTED = 1, LEN_OK = 2, VEC_OK = 4 };
+  size_t d = 0, first = 0;            // `first`: chain index of kind[0]
+  std::vector<double> models;         // [L + 1][d]: blocks first-1 .. first+L-1
+  std::vector<int32_t> kind;          // [L]
+  std::vector<int32_t> offsets;       // [L + 1] CSR into the update arrays
+  std::vector<u8> commits;            // [n][64]
+  std::vector<int32_t> flags;         // [n]
+  std::vector<int32_t> plain_update;  // [np] update index of each plain row
+  std::vector<double> plain_delta;    // [np][d]
+};
+
 struct Blockchain {
   std::vector<Block> blocks;
+  // from >= 1 (the genesis block has no step to audit); to is clamped to the chain's length
+  AuditArrays audit_arrays(size_t d, size_t from, size_t to) const;
   static Blockchain with_genesis(size_t num_features);
   static Block genesis(size_t num_features);
   // NewBlock semantics: timestamp 0 for empty blocks, else `now_unix` (block.go:30-44)

@@ -108,6 +108,65 @@ static void test_shares_and_ledger() {
   CHECK(!chain.print_chain().empty());
 }
 
+// The chain audit's array view of a chain: every kind of block, a commitment of the wrong length, a delta
+// vector of the wrong length, a model of the wrong width, an empty range, and the strict marshal check.
+static void test_chain_audit_arrays() {
+  const size_t d = 5;
+  const std::vector<G1> pk = gen_commit_key_g1(d, Scalar::from_i64(2));
+  const Bytes cm = commit({3, -4, 0, 1ll << 33, 7}, pk, 0).marshal();
+  Blockchain chain = Blockchain::with_genesis(d);
+  auto add = [&](std::vector<double> w, std::vector<Update> us, i64 it) {
+    BlockData bd;
+    bd.iteration = it;
+    bd.global_w = std::move(w);
+    bd.deltas = std::move(us);
+    chain.append(chain.make_block(bd, {{0, 10}}, 1000 + it));
+  };
+  Update sec;
+  sec.commitment = cm;
+  sec.accepted = true;
+  Update shortc = sec;
+  shortc.commitment.resize(63);
+  Update plain = sec;
+  plain.delta = {1, 2, 3, 4, 5};
+  Update plain_short = sec;
+  plain_short.delta = {1, 2};
+  plain_short.accepted = false;
+  Update bare;
+  add({1, 2, 3, 4, 5}, {sec, shortc}, 0);          // SECAGG, second commitment of 63 bytes
+  add({1, 2, 3, 4, 5}, {}, 1);                     // EMPTY
+  add({2, 4, 6, 8, 10}, {plain, plain_short}, 2);  // PLAIN, second vector of 2 entries
+  add({2, 4, 6}, {bare}, 3);                       // NONE, and a model of the wrong width
+  const AuditArrays a = chain.audit_arrays(d, 1, 99);
+  CHECK(a.first == 1 && a.kind.size() == 4 && a.models.size() == 5 * d);
+  CHECK(a.kind[0] == AuditArrays::SECAGG && a.kind[1] == AuditArrays::EMPTY && a.kind[2] == AuditArrays::PLAIN &&
+        a.kind[3] == AuditArrays::NONE);
+  CHECK((a.offsets == std::vector<int32_t>{0, 2, 2, 4, 4}));
+  CHECK(a.commits.size() == 4 * 64 && a.flags.size() == 4);
+  CHECK(a.flags[0] == (AuditArrays::ACCEPTED | AuditArrays::LEN_OK) && a.flags[1] == AuditArrays::ACCEPTED);
+  CHECK(a.flags[2] == (AuditArrays::ACCEPTED | AuditArrays::LEN_OK | AuditArrays::VEC_OK));
+  CHECK(a.flags[3] == AuditArrays::LEN_OK);
+  CHECK(std::memcmp(a.commits.data(), cm.data(), 64) == 0);
+  for (size_t i = 64; i < 128; ++i) CHECK(a.commits[i] == 0);
+  CHECK((a.plain_update == std::vector<int32_t>{2, 3}) && a.plain_delta.size() == 2 * d);
+  CHECK(a.plain_delta[4] == 5.0 && a.plain_delta[d] == 0.0);
+  CHECK(a.models[0] == 0.0 && a.models[d + 4] == 5.0 && a.models[4 * d] != a.models[4 * d]);   // NaN row
+  const AuditArrays part = chain.audit_arrays(d, 3, 4);
+  CHECK(part.first == 3 && part.kind.size() == 1 && part.models.size() == 2 * d && part.flags.size() == 2);
+  const AuditArrays none = chain.audit_arrays(d, 5, 9);
+  CHECK(none.kind.empty() && none.models.empty() && none.offsets.size() == 1);
+  CHECK(G1::marshaled_valid(cm.data()));
+  CHECK(G1::marshaled_valid(Bytes(64, 0).data()));
+  Bytes bad = cm;
+  bad[63] ^= 1;
+  CHECK(!G1::marshaled_valid(bad.data()));
+  Bytes big = cm;   // x + p: the same point to a reducing decoder, refused by the strict one
+  U256 xp;
+  add_u256(xp, U256::from_be(cm.data()), PRIME());
+  xp.to_be(big.data());
+  if (cmp(xp, PRIME()) >= 0 && cmp(xp, U256::from_be(cm.data())) > 0) CHECK(!G1::marshaled_valid(big.data()));
+}
+
 static void test_protocol() {
   ProtocolConfig pc;
   pc.num_nodes = 30;
@@ -173,6 +232,7 @@ int main(int argc, char** argv) {
         if (t < 2) test_pairing();
         test_vrf();
         test_shares_and_ledger();
+        test_chain_audit_arrays();
         test_protocol();
         test_pool(t);
       }

@@ -37,6 +37,8 @@ SIGNATURES = {
     "bsc_marshal": [P, I, P, P],
     "bsc_to_affine": [P, I, P, P],
     "bsc_chunk_check": [P, I, I, P, I, I, P, I, I, P, P],
+    "bsc_g1_unmarshal": [P, I, P, P, P, P],
+    "bsc_chain_audit": [P, P, P, I, I, P, P, P, I, P, P, I, P, I, I, D, D, D, I, P, P, P, P, P, P, P, P, P],
     # vrf.hip
     "bsc_vrf_prove": [P, P, P, P, I, I, P, P, P, P, P],
     "bsc_vrf_prove_p": [P, P, P, P, I, I, P, P, P, P, I, P],

@@ -252,6 +252,53 @@ class DeviceCommitEngine:
             cache[key] = torch.from_numpy(rows.reshape(-1).astype(np.int64)).to(self.device)
         return cache[key]
 
+    AUDIT_SLAB = 256   # rows per pass of the chain audit (kernels/msm.hip bsc_chain_audit: why 256)
+
+    def audit_chain(self, models: np.ndarray, kind: np.ndarray, offsets: np.ndarray, commits: np.ndarray,
+                    len_ok: np.ndarray, plain: np.ndarray, pbeg: np.ndarray, res: np.ndarray, scale: float,
+                    tol: float, wmax: float, slab: int | None = None) -> np.ndarray:
+        """The device backend of protocol/chain_audit.py (kernels/msm.hip bsc_chain_audit), host arrays in and out:
+        models fp64 [L + 1, d]; kind int32 [L]; offsets int32 [L + 1] (CSR into commits uint8 [n, 64], len_ok int32
+        [n]); plain fp64 [np, d] update vectors of the plain blocks with their commitment at pbeg int32 [np]; res
+        int32 [2 L + 2 np] = status | first | plain status | plain first as the caller pre-set them.  Returns res
+        after the audit.  Everything is queued on the current stream; one read-back at the end."""
+        L, n, npl = int(kind.size), int(len_ok.size), int(pbeg.size)
+        slab = int(slab or self.AUDIT_SLAB)
+        assert 1 <= slab <= 4096
+        assert models.dtype == np.float64 and (L == 0 or models.shape == (L + 1, self.d))
+        assert kind.dtype == np.int32 and offsets.dtype == np.int32 and offsets.size == L + 1
+        assert commits.dtype == np.uint8 and commits.shape == (n, 64) and len_ok.dtype == np.int32
+        assert plain.dtype == np.float64 and plain.shape == (npl, self.d) and pbeg.dtype == np.int32
+        assert res.dtype == np.int32 and res.size == 2 * L + 2 * npl
+        if L and (int(offsets[0]) != 0 or int(offsets[-1]) > n or (np.diff(offsets) < 0).any()):
+            raise ValueError("audit_chain: offsets are not a CSR array over the commitments")
+        if npl and (int(pbeg.min()) < 0 or int(pbeg.max()) >= n):
+            raise ValueError("audit_chain: a plain row's commitment index is out of range")
+        if L == 0 and npl == 0:
+            return res.copy()
+        dev = self.device
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        t_models, t_kind, t_off, t_com, t_len = up(models), up(kind), up(offsets), up(commits), up(len_ok)
+        t_plain, t_pbeg, t_pend, t_res = up(plain), up(pbeg), up(pbeg + 1), up(res)
+        nb = min(slab, max(L, npl))
+        nslab = (self.d + 1023) // 1024
+        coeffs = torch.empty((nb, self.d), dtype=torch.int64, device=dev)
+        rows = torch.arange(nb, dtype=torch.int32, device=dev)
+        partial = torch.empty((nb * nslab, 24), dtype=torch.int32, device=dev)
+        msm = torch.empty((nb, 24), dtype=torch.int32, device=dev)
+        aff = torch.empty((max(n, 1), 16), dtype=torch.int32, device=dev)
+        valid = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+        h_res = torch.empty((res.size,), dtype=torch.int32, pin_memory=True)
+        _check(hip().bsc_chain_audit(_ptr(t_models), _ptr(t_kind), _ptr(t_off), L, self.d, _ptr(t_plain), _ptr(t_pbeg),
+                                     _ptr(t_pend), npl, _ptr(t_com), _ptr(t_len), n, _ptr(self.tbl_pk), self.b0,
+                                     self.nw, float(scale), float(tol), float(wmax), slab, _ptr(coeffs), _ptr(rows),
+                                     _ptr(partial), _ptr(msm), _ptr(aff), _ptr(valid), _ptr(t_res),
+                                     h_res.data_ptr(), _stream()), "chain_audit")
+        S.host_wait(S.record())
+        return h_res.numpy().copy()
+
     def commitments(self, pts: torch.Tensor) -> torch.Tensor:
         """Full-vector commitment per row = sum of its chunk commitments. Returns Jacobian [n, 24]."""
         n, nch, S, _ = pts.shape
@@ -306,6 +353,20 @@ def marshal(pts: torch.Tensor) -> torch.Tensor:
     out = torch.empty((flat.shape[0], 64), dtype=torch.uint8, device=pts.device)
     _check(hip().bsc_marshal(_ptr(flat), flat.shape[0], _ptr(out), _stream()), "marshal")
     return out
+
+
+def g1_unmarshal(data: torch.Tensor, pre: torch.Tensor | None = None):
+    """kyber marshal bytes uint8 [n, 64] -> (affine Montgomery int32 [n, 16], valid int32 [n]), the inverse of
+    marshal().  Valid: all zeros (infinity) or x, y < p on the curve; an invalid point comes back as infinity.
+    pre: optional int32 [n], 0 = invalid whatever the bytes."""
+    assert data.dtype == torch.uint8 and data.dim() == 2 and data.shape[1] == 64
+    n = data.shape[0]
+    assert pre is None or (pre.dtype == torch.int32 and pre.numel() == n)
+    out = torch.empty((n, 16), dtype=torch.int32, device=data.device)
+    valid = torch.empty((n,), dtype=torch.int32, device=data.device)
+    _check(hip().bsc_g1_unmarshal(_ptr(data.contiguous()), n, _ptr(pre), _ptr(out), _ptr(valid), _stream()),
+           "g1_unmarshal")
+    return out, valid
 
 
 def to_affine(pts: torch.Tensor) -> torch.Tensor:

@@ -44,6 +44,9 @@ def main(argv=None) -> int:
     add_framework_flags(ap)
     ap.add_argument("--rounds", type=int, default=None, help="stop after this many rounds")
     ap.add_argument("--print-chain", default="rank0", choices=["rank0", "all", "none"])
+    ap.add_argument("--audit-chain", action="store_true",
+                    help="audit each block's model step against its commitments (protocol/chain_audit.py): a "
+                         "resumed chain before the first round (a failure ends the run), and the chain at the end")
     ap.add_argument("--rpc-listen", default=None, help="HOST:PORT: serve the Peer net/rpc methods (rank 0)")
     ap.add_argument("--rpc-flood", default="", help="comma list of HOST:PORT peers that receive every block")
     ap.add_argument("--rpc-peer", action="store_true",
@@ -85,6 +88,13 @@ def main(argv=None) -> int:
         srv = netrpc.RpcServer(svc.handlers(), host, int(port), max_conns=netrpc.conns_for(cfg.num_nodes),
                                max_message=netrpc.message_limit(eng.d, cfg.num_nodes)).start()
         eng.log.info("serving Peer net/rpc on %s:%d", *srv.addr)
+    if ns.audit_chain and cfg.resume and len(eng.fsm.chain) > 1:
+        res = _audit(eng)
+        if not res.ok:
+            eng.log.info("the resumed chain fails its audit: not continuing")
+            eng.close()
+            comm.shutdown()
+            return 1
     n = 0
     while ns.rounds is None or n < ns.rounds:
         r = eng.run_round(last=ns.rounds is not None and n == ns.rounds - 1) if hasattr(eng, "drain") \
@@ -106,6 +116,8 @@ def main(argv=None) -> int:
         n += 1
     if srv is not None:
         srv.close()
+    if ns.audit_chain:
+        _audit(eng)
     if cfg.colluders > 0:
         print(eng.stats["unmasked_updates"], eng.stats["total_updates"], cfg.colluders / 100.0, cfg.num_noisers)
     if ns.print_chain == "all" or (ns.print_chain == "rank0" and comm.rank == 0):
@@ -145,6 +157,21 @@ def _rpc_peer_main(cfg, ns) -> int:
     finally:
         peer.close()
     return 0
+
+
+def _audit(eng):
+    """--audit-chain: the engine's chain against its commitments, with the engine's own tables on a GPU (no second
+    set is built); logs one line per block that is not OK or EMPTY and the summary."""
+    from .protocol.chain_audit import audit_chain
+
+    dev_eng = getattr(eng.crypto, "eng", None)
+    res = audit_chain(eng.fsm.chain, getattr(eng.crypto, "key", None), precision=eng.cfg.precision,
+                      device=None if dev_eng is not None else "cpu", engine=dev_eng)
+    for ln in res.lines():
+        eng.log.info("%s", ln)
+    eng.log.info("%s", res.summary())
+    eng.stats["chain_audit_ok"] = int(res.ok)
+    return res
 
 
 def _noise_row(eng, peer: int, it: int):

@@ -235,3 +235,190 @@ extern "C" int bsc_kzg_rlc(const uint32_t* csum, const uint32_t* wsum, const lon
   hipLaunchKernelGGL(k_kzg_reduce, dim3(1), dim3(KZ_THREADS), 0, (hipStream_t)stream, partial, nb, out);
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------ per-row audit (--kzg-audit shares)
+// The same triple for every row (worker update) of the share MSM's output on its own, read in place:
+// pts [n][nch][T+1][24] (slots 0..T-1 the witnesses, slot T the chunk commitment), ys [n][nch][T].
+// Row i draws its weights from its own seed s_i = kzg_r(seed, 2^40 + i), r_ikj = kzg_r(s_i, k*npts + j),
+// so its triple is the aggregate audit's of (C_i, W_i, y_i) under s_i and the rows' sum is an RLC over all of them.
+//
+// MI355X mapping: n times the aggregate audit's chains, so the witness terms share their doublings.  A lane
+// keeps one share point j and KR_M chunks; all its terms go through ONE accumulator, Straus fashion:
+//     acc = 2 acc;  acc += W_k for every chunk k of the lane whose r_ikj has the bit set
+// -- 64 doublings per lane instead of 64 per term, the weights recomputed from the seed (a few integer
+// multiplications beside a 16-product addition) and the witnesses re-read from L1/L2 (24 KB per block), so the
+// lane holds no table and indexes no private array.  x_j multiplies the lane's sum once at the end.  A wave
+// holds 64 / npts groups of lanes over a slab of KR_M * groups chunks (a 64-thread block; (slab, row) grid:
+// ~2300 witness blocks for MNIST's 35 rows x 785 chunks x 21 points).  R_ik C_ik - Z_ik B_k is one joint chain per
+// chunk, 64 chunks per block, in blocks of their own behind the witness blocks.  One LDS tree per block
+// output, then a block per row over the row's partials and k_kzg_reduce over the rows for the total.
+namespace {
+
+constexpr int KR_M = 4;   // chunks per lane: 8 + 16 KR_M products per bit instead of 24 KR_M
+
+__device__ __forceinline__ void shl192(unsigned long long& k0, unsigned long long& k1, unsigned long long& k2, int sh) {
+  while (sh >= 64) { k2 = k1; k1 = k0; k0 = 0; sh -= 64; }
+  if (sh) {
+    k2 = (k2 << sh) | (k1 >> (64 - sh));
+    k1 = (k1 << sh) | (k0 >> (64 - sh));
+    k0 <<= sh;
+  }
+}
+
+__device__ __forceinline__ int bits192(unsigned long long k0, unsigned long long k1, unsigned long long k2) {
+  if (k2) return 192 - __clzll(k2);
+  if (k1) return 128 - __clzll(k1);
+  if (k0) return 64 - __clzll(k0);
+  return 0;
+}
+
+}  // namespace
+
+// grid (nslab + nl1, n).  Blocks x < nslab: witness terms of chunks [x * slab, +slab) -> partial (A, L2);
+// blocks x >= nslab: the commitment terms of chunks [(x - nslab) * 64, +64) -> partial (L1, -).
+// partial [n][gridDim.x][2][24].  A row whose flag is 0 is not read (its blocks leave at once).
+extern "C" __global__ void __launch_bounds__(KZ_THREADS) k_kzg_rows(
+    const uint32_t* __restrict__ pts, const long long* __restrict__ ys, const int* __restrict__ alive,
+    const int* __restrict__ cols, const int* __restrict__ xs, int nch, int T, int npts, int nslab,
+    const uint32_t* __restrict__ bases, int base_stride, unsigned long long seed, uint32_t* __restrict__ partial) {
+  __shared__ uint32_t lds[KZ_THREADS * 24];
+  const int i = blockIdx.y, bx = blockIdx.x, t = threadIdx.x;
+  if (alive != nullptr && alive[i] == 0) return;   // block-uniform
+  const unsigned long long s = kzg_r(seed, (1ull << 40) + (unsigned long long)i);
+  const long long cstride = (long long)(T + 1) * 24;
+  const uint32_t* prow = pts + (long long)i * nch * cstride;
+  const long long* yrow = ys + (long long)i * nch * T;
+  jac u = jac_inf(), v = jac_inf();
+  if (bx < nslab) {
+    const int G = KZ_THREADS / npts;
+    const int g = t / npts, j = t % npts;
+    const int c = t < G * npts ? cols[j] : -1;
+    if ((unsigned)c < (unsigned)T) {   // (a column outside the row's slots contributes nothing: the check then fails)
+      const int k0 = bx * G * KR_M + g;
+      const uint32_t* w0 = prow + (long long)c * 24;
+      for (int b = 63; b >= 0; --b) {
+        u = kz_dbl(u);
+#pragma unroll 1
+        for (int m = 0; m < KR_M; ++m) {
+          const int k = k0 + m * G;
+          if (k < nch) {
+            const unsigned long long r = kzg_r(s, (unsigned long long)k * npts + j);
+            if ((r >> b) & 1ull) u = jac_add(u, ld_jac(w0 + (long long)k * cstride));
+          }
+        }
+      }
+      const int x = xs[j];
+      const unsigned ax = x < 0 ? unsigned(-x) : unsigned(x);
+      v = jac_mul_192(u, ax, 0, 0);
+      if (x < 0) v = jac_neg(v);
+    }
+  } else {
+    const int k = (bx - nslab) * KZ_THREADS + t;
+    if (k < nch) {
+      // R = sum_j r (128-bit), Z = sum_j r * y (two's complement over 192 bits)
+      unsigned long long r0 = 0, r1 = 0, r2 = 0, z0 = 0, z1 = 0, z2 = 0;
+      for (int j = 0; j < npts; ++j) {
+        const int c = cols[j];
+        if ((unsigned)c >= (unsigned)T) continue;
+        const unsigned long long r = kzg_r(s, (unsigned long long)k * npts + j);
+        r0 += r;
+        r1 += r0 < r;
+        const long long y = yrow[(long long)k * T + c];
+        const unsigned long long m = y < 0 ? 0ull - (unsigned long long)y : (unsigned long long)y;
+        unsigned long long p0 = r * m, p1 = __umul64hi(r, m), p2 = 0;
+        if (y < 0) {   // negate the 192-bit product
+          p0 = ~p0; p1 = ~p1; p2 = ~0ull;
+          p0 += 1;
+          const unsigned long long c0 = p0 == 0;
+          p1 += c0;
+          p2 += (c0 && p1 == 0);
+        }
+        z0 += p0;
+        const unsigned long long c0 = z0 < p0;
+        const unsigned long long t1 = z1 + p1;
+        const unsigned long long c1 = t1 < z1;
+        z1 = t1 + c0;
+        const unsigned long long c1b = z1 < c0;
+        z2 += p2 + c1 + c1b;
+      }
+      const bool neg = z2 >> 63;
+      if (neg) {
+        z0 = ~z0; z1 = ~z1; z2 = ~z2;
+        z0 += 1;
+        const unsigned long long c0 = z0 == 0;
+        z1 += c0;
+        z2 += (c0 && z1 == 0);
+      }
+      const jac C = ld_jac(prow + (long long)k * cstride + (long long)T * 24);
+      aff B = ld_aff(bases + (long long)k * base_stride * 16);
+      if (!neg) B = aff_neg(B);   // the term is -Z B
+      // R C + |Z| (+-B): one chain over the longer scalar, both left-aligned at bit 191
+      const int nr = bits192(r0, r1, r2), nz = bits192(z0, z1, z2);
+      const int nbits = nr > nz ? nr : nz;
+      shl192(r0, r1, r2, 192 - nbits);
+      shl192(z0, z1, z2, 192 - nbits);
+      for (int b = 0; b < nbits; ++b) {
+        u = kz_dbl(u);
+        if (r2 >> 63) u = jac_add(u, C);
+        if (z2 >> 63) u = jac_add_aff(u, B);
+        r2 = (r2 << 1) | (r1 >> 63); r1 = (r1 << 1) | (r0 >> 63); r0 <<= 1;
+        z2 = (z2 << 1) | (z1 >> 63); z1 = (z1 << 1) | (z0 >> 63); z0 <<= 1;
+      }
+    }
+  }
+  u = block_sum(u, lds);
+  if (bx < nslab) v = block_sum(v, lds);
+  if (t == 0) {
+    uint32_t* o = partial + ((long long)i * gridDim.x + bx) * 48;
+    st_jac(o, u);
+    st_jac(o + 24, v);
+  }
+}
+
+// out[i] = (L1, A, L2) of row i from its block partials, one block per row; three infinities for a skipped row
+extern "C" __global__ void __launch_bounds__(KZ_THREADS) k_kzg_rows_reduce(const uint32_t* __restrict__ partial,
+                                                                           const int* __restrict__ alive, int nslab,
+                                                                           int nb, uint32_t* __restrict__ out) {
+  __shared__ uint32_t lds[KZ_THREADS * 24];
+  const int i = blockIdx.x, t = threadIdx.x;
+  const bool on = alive == nullptr || alive[i] != 0;   // block-uniform
+  const uint32_t* p = partial + (long long)i * nb * 48;
+  for (int s = 0; s < 3; ++s) {
+    jac v = jac_inf();
+    if (on) {
+      // L1: the first point of the commitment blocks; A, L2: the two points of the witness blocks
+      const int lo = s == 0 ? nslab : 0, hi = s == 0 ? nb : nslab;
+      for (int b = lo + t; b < hi; b += KZ_THREADS) v = jac_add(v, ld_jac(p + (long long)b * 48 + (s == 2 ? 24 : 0)));
+      v = block_sum(v, lds);
+    }
+    if (t == 0) st_jac(out + (long long)i * 72 + s * 24, v);
+  }
+}
+
+// Blocks of one row (witness slabs, commitment blocks) for bsc_kzg_rlc_rows' partial scratch [n][blocks][48].
+extern "C" int bsc_kzg_rows_blocks(int nch, int npts) {
+  if (nch <= 0 || npts <= 0 || npts > 32) return 0;
+  const int slab = (KZ_THREADS / npts) * KR_M;
+  return (nch + slab - 1) / slab + (nch + KZ_THREADS - 1) / KZ_THREADS;
+}
+
+// pts int32 [n][nch][T+1][24], ys int64 [n][nch][T] (a view of the share MSM's ring: native strides), alive int32 [n]
+// or null, cols / xs int32 [npts] (share slots and their x, npts <= 32), bases affine as in bsc_kzg_rlc (nch_round =
+// nch), partial [n * bsc_kzg_rows_blocks][48], out [n + 1][3][24]: row i's (L1, A, L2), row n their sums.
+extern "C" int bsc_kzg_rlc_rows(const uint32_t* pts, const long long* ys, const int* alive, const int* cols,
+                                const int* xs, int n, int nch, int T, int npts, const uint32_t* bases, int base_stride,
+                                unsigned long long seed, uint32_t* partial, uint32_t* out, void* stream) {
+  if (n < 0 || nch < 0 || npts < 0) return -1;
+  if (n == 0 || npts == 0 || nch == 0) return 0;
+  if (npts > 32 || T <= 0 || npts > T || base_stride < 0 || n > 65535) return -1;
+  if (!pts || !ys || !cols || !xs || !bases || !partial || !out) return -1;
+  const int slab = (KZ_THREADS / npts) * KR_M;
+  const int nslab = (nch + slab - 1) / slab;
+  const int nb = bsc_kzg_rows_blocks(nch, npts);
+  hipLaunchKernelGGL(k_kzg_rows, dim3(nb, n), dim3(KZ_THREADS), 0, (hipStream_t)stream, pts, ys, alive, cols, xs, nch, T,
+                     npts, nslab, bases, base_stride, seed, partial);
+  hipLaunchKernelGGL(k_kzg_rows_reduce, dim3(n), dim3(KZ_THREADS), 0, (hipStream_t)stream, partial, alive, nslab, nb,
+                     out);
+  hipLaunchKernelGGL(k_kzg_reduce, dim3(1), dim3(KZ_THREADS), 0, (hipStream_t)stream, out, n, out + (long long)n * 72);
+  return (int)hipGetLastError();
+}

@@ -75,6 +75,12 @@ def u32_tensor(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(device)
 
 
+def kzg_row_seed(seed: int, i: int) -> int:
+    """The RLC seed s_i of row i of a per-row audit (kzg.hip k_kzg_rows): kzg_r(seed, 2^40 + i), so row i's weights
+    are r_ikj = kzg_r(s_i, k * npts + j) -- those of kzg_rlc_host under s_i."""
+    return int(rt().kzg_r(int(seed) & ((1 << 64) - 1), (1 << 40) + int(i)))
+
+
 class DeviceCommitEngine:
     """Commitment key + witness-base tables resident on one GPU.
 
@@ -238,6 +244,40 @@ class DeviceCommitEngine:
         _check(lib.bsc_kzg_rlc(_ptr(csum.contiguous()), _ptr(wsum.contiguous()), _ptr(ys.contiguous()),
                                _ptr(xs.contiguous()), nch, npts, int(spm), _ptr(bases), stride, self.nchunks,
                                int(seed) & ((1 << 64) - 1), _ptr(partial), _ptr(out), _stream()), "kzg_rlc")
+        return out
+
+    def kzg_rlc_rows(self, pts: torch.Tensor, ys: torch.Tensor, cols: torch.Tensor, xs: torch.Tensor,
+                     alive: torch.Tensor | None = None, literal: bool = False, seed: int = 0) -> torch.Tensor:
+        """The audit's triple per row of the share MSM's output (kzg.hip, bsc_kzg_rlc_rows): Jacobian int32
+        [n + 1, 3, 24], row i = (L1, A, L2) of worker row i over the share slots cols (int32 [npts] at x = xs, npts <=
+        32) under the seed kzg_row_seed(seed, i), row n the three sums over the rows.
+
+        pts [n, nchunks, T+1, 24] / ys int64 [n, nchunks, T] are read in place (shares()' outputs or a leading
+        view of the speculative ring); alive: optional int32 [n] -- a row with flag 0 is never read (the MSM leaves it
+        undefined) and gives three points at infinity."""
+        n = pts.shape[0]
+        nch, T = self.nchunks, self.T
+        assert pts.dtype == torch.int32 and tuple(pts.shape) == (n, nch, T + 1, 24) and pts.is_contiguous()
+        assert ys.dtype == torch.int64 and tuple(ys.shape) == (n, nch, T) and ys.is_contiguous()
+        assert cols.dtype == torch.int32 and xs.dtype == torch.int32 and cols.dim() == 1 and cols.shape == xs.shape
+        npts = cols.numel()
+        assert npts <= min(32, T), "at most 32 share points"
+        if alive is not None:
+            assert alive.dtype == torch.int32 and tuple(alive.shape) == (n,)
+        out = torch.empty((n + 1, 3, 24), dtype=torch.int32, device=self.device)
+        if n == 0 or npts == 0:
+            return out.zero_()   # z = 0: points at infinity
+        if literal:
+            if getattr(self, "_g1_aff", None) is None:
+                self._g1_aff = u32_tensor(rt().g1_affine_mont_u32(rt().g1_generator()), self.device)
+            bases, stride = self._g1_aff, 0
+        else:
+            bases, stride = self.pk_aff, self.poly
+        lib = hip()
+        partial = torch.empty((n * lib.bsc_kzg_rows_blocks(nch, npts), 48), dtype=torch.int32, device=self.device)
+        _check(lib.bsc_kzg_rlc_rows(_ptr(pts), _ptr(ys), _ptr(alive), _ptr(cols.contiguous()), _ptr(xs.contiguous()),
+                                    n, nch, T, npts, _ptr(bases), stride, int(seed) & ((1 << 64) - 1), _ptr(partial),
+                                    _ptr(out), _stream()), "kzg_rlc_rows")
         return out
 
     def kzg_order(self, npts: int, spm: int) -> torch.Tensor:
@@ -485,6 +525,10 @@ class NativeSecAgg:
                                             _ptr(self.cs), _ptr(self.ok), self.h_status.data_ptr(), self.h_W.data_ptr(),
                                             self.h_ok.data_ptr()), "round_bind_outputs")
         self._layouts: list = []   # keeps each layout's tensors alive
+        # events the side stream waits for before a speculative MSM rewrites a ring slot (keyed by the slot's pts
+        # address): the per-worker KZG audit reads the slot in place.  Empty unless that audit is on
+        self.slot_guards: dict = {}
+        self._side = side
         self.world = 0            # several ranks: set by gather_buffers()
         self.h_clock = None
         self._out = (ctypes.c_int * 2)()
@@ -769,6 +813,10 @@ class NativeSecAgg:
                                  _ptr(sl["rows"]), ev_up, ev_flags, ev_up.cuda_event, ev_flags.cuda_event,
                                  _ptr(self.eng.tbl_wb))
         h_np, h_ptr, pts_p, ys_p, rows_p, ev_up, ev_flags, ev_up_h, ev_flags_h, wb_p = lp
+        if self.slot_guards:
+            g = self.slot_guards.pop(pts_p, None)
+            if g is not None:
+                self._side.wait_event(g)
         h_np[:n] = rows
         _check(hip().bsc_round_spec_msm2(self.ctx, k, ev_wait.cuda_event if ev_wait is not None else None,
                                          qdelta.data_ptr(), h_ptr, n, wb_p, 2 if no_commit else 0, int(group_rows),

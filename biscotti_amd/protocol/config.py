@@ -86,7 +86,11 @@ class RunConfig:
     #                                 the aggregate: off | consistent (y against PK[poly*k]) | literal (y
     #                                 against G1: the reference's formula, which only chunk 0 satisfies, Q9).
     #                                 Device RLC sums (kzg.hip) + one host 3-pairing product per batch of
-    #                                 rounds, joined lazily; failures are counted and logged, never block the chain
+    #                                 rounds, joined lazily; failures are counted and logged, never block the chain.
+    #                                 shares: the consistent check per worker update instead of per aggregate (one
+    #                                 row kernel over the share MSM's output + one pairing product per block; a
+    #                                 failing block is re-checked row by row and its peers are named): stats
+    #                                 kzg_share_checks / kzg_share_failures
     ablation: str = ""              # comma list of semantic / pipeline ablations (experiments and tests only):
     #   noise_independent  each worker draws private noise instead of its noisers' shared pre-sampled
     #                      vectors (client_obj.py:97-98 shares them; docs/ROBUSTNESS.md)
@@ -213,8 +217,8 @@ class RunConfig:
             err.append(f"defense {self.defense!r}: expected KRUM | RONI | LSH")
         if self.miner_threshold not in self.MINER_THRESHOLDS:
             err.append(f"miner_threshold {self.miner_threshold!r}: expected {' | '.join(self.MINER_THRESHOLDS)}")
-        if self.kzg_audit not in ("off", "consistent", "literal"):
-            err.append(f"kzg_audit {self.kzg_audit!r}: expected off | consistent | literal")
+        if self.kzg_audit not in ("off", "consistent", "literal", "shares"):
+            err.append(f"kzg_audit {self.kzg_audit!r}: expected off | consistent | literal | shares")
         if err:
             raise ValueError("invalid RunConfig: " + "; ".join(err))
 
@@ -315,7 +319,7 @@ def add_framework_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--vrf-audit", dest="vrf_audit", action="store_true",
                     help="verify every VRF proof this rank produces (device batches in place, K16); failures "
                          "are counted and logged, never change the chain")
-    ap.add_argument("--kzg-audit", default="off", choices=["off", "consistent", "literal"],
+    ap.add_argument("--kzg-audit", default="off", choices=["off", "consistent", "literal", "shares"],
                     help="batched verifySecret over each round's aggregate (K13)")
     ap.add_argument("--comm-timeout", dest="comm_timeout_s", type=float, default=300.0)
     ap.add_argument("--fail-at", type=int, default=-1, help="fault injection: die after committing this iteration")

@@ -336,6 +336,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
             t0 = time.perf_counter()
             if self._kzg_pending or self._kzg_stage:
                 self._kzg_poll(final=True)
+            if self.cfg.kzg_audit == "shares":
+                self._kzg_share_summary()
             work, self._pre_vrf_work = self._pre_vrf_work, []
             for f in work:   # the run's last signature batch: nothing else needs the host threads now
                 f(None, threads=max(1, self.cfg.host_threads))

@@ -153,6 +153,7 @@ class RoundHeadMixin:
                         spec = (spec_workers, self.crypto.shares_async(qdelta, [row_of[w] for w in spec_workers],
                                                                        self.side_stream,
                                                                        group_rows=SPEC_GROUP_ROWS))
+                        spec[1].peers = list(spec_workers)   # (the per-worker KZG audit names them)
             # full-vector commitments on the background stream: their first consumer is the signing after
             # Krum, so noise + Krum on the main stream do not queue behind them
             pending_commits = pre["commits"] if use_pre else \
@@ -376,6 +377,7 @@ class RoundHeadMixin:
             with S.use(self.upload_stream):
                 sp = self.crypto.shares_async(pre["qdelta"], rows, side, group_rows=SPEC_GROUP_ROWS,
                                               no_commit=no_commit)
+        sp.peers = list(spec_workers)   # the worker of each row (the per-worker KZG audit names them)
         return sp
 
     def _spec_horizon(self) -> int:

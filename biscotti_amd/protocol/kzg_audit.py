@@ -7,6 +7,10 @@ ONE host three-pairing product per batch (pairing.cpp, prepared G2 lines).  Only
 in the chain are audited (staged when the block is adopted, not when the aggregate is queued), and a
 failed batch is re-checked round by round so failures are attributed to the right iterations.
 Failures are counted and logged; they never block the chain.
+
+--kzg-audit shares runs the consistent check per worker update instead: one row kernel over the share MSM's
+output where it lies (kzg.hip k_kzg_rows; every row's triple under a seed of its own, and their sum), one pairing
+product on the summed triple per block and, only if that fails, one per audited row to name the workers.
 """
 from __future__ import annotations
 
@@ -24,6 +28,9 @@ class KzgAuditMixin:
         self._kzg_stage: list = []     # rounds waiting for the next device launch
         if cfg.kzg_audit != "off":
             self.stats.update(kzg_checks=0, kzg_failures=0)
+            if cfg.kzg_audit == "shares":
+                self.stats.update(kzg_share_checks=0, kzg_share_failures=0)
+                self.kzg_share_blame: list = []   # (iteration, peer id) of every failing worker update
             # G2 side = (g2key[0], g2key[1]) = (G2, s G2)
             self._kzg_g2 = (self.R.g2_generator(), self._commit_key_g2_1(cfg.commit_key))
             self._kzg_rng = np.random.default_rng([cfg.seed, self.comm.rank, 0x6B7A67])
@@ -47,6 +54,10 @@ class KzgAuditMixin:
         """The aggregate `agg` (from _aggregate) is in the chain: stage its audit.  Device path: the
         audit stream waits for the events recorded where the sums were produced (not for work queued
         since), then the inputs join the batch."""
+        rows = agg.get("kzg_rows")
+        if rows is not None:   # --kzg-audit shares: launched when the aggregate was queued (GPU), or checked here
+            self._kzg_pending.append(rows if self.gpu else self._kzg_host_rows(*rows, agg["xs"], it))
+            return
         kin = agg.get("kzg_in")
         if kin is None:
             return
@@ -110,6 +121,75 @@ class KzgAuditMixin:
                                   int(self._kzg_rng.integers(0, 2**63)), self.cfg.host_threads)
         self._kzg_pending.append({"its": [it], "ok": self.R.kzg_check(*pts, *self._kzg_g2)})
 
+    # ---------------------------------------------------------------- per worker (--kzg-audit shares)
+    def _kzg_rows_launch(self, pts, ys, alive, cols, xs, rows, it) -> dict:
+        """Queue the row sums of one aggregation on the current (audit) stream and their read-back: pts / ys the share
+        MSM's output rows in place, alive their flags (a copy), cols / xs the layout's contributing share slots, rows
+        the worker id of each row.  Returns the pending entry (_kzg_poll decides it once the block is adopted)."""
+        n = pts.shape[0]
+        out = self.crypto.eng.kzg_rlc_rows(pts, ys, cols, xs, alive=alive, seed=int(self._kzg_rng.integers(0, 2**63)))
+        host = torch.empty((n + 1, 3, 24), dtype=torch.int32, pin_memory=True)
+        flags = torch.empty((n,), dtype=torch.int32, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        flags.copy_(alive, non_blocking=True)
+        return {"its": [it], "ev": S.record(), "host": host, "flags": flags, "rows": list(rows), "job": None}
+
+    def _kzg_host_rows(self, flat, ys, rows_l, peers, ccols, ycols_t, xs, it) -> dict:
+        """CPU path: each kept row's RLC and pairing product on the host (native threads), under the seeds the
+        device uses."""
+        from ..ops.bn256 import kzg_row_seed
+
+        nch, T = self.nchunks, self.T
+        cc, yc = ccols.numpy(), ycols_t.numpy()
+        bases = [self.crypto.key.point(self.cfg.poly_size * k) for k in range(nch)]
+        seed = int(self._kzg_rng.integers(0, 2**63))
+        bad = []
+        for i, (r, w) in enumerate(zip(rows_l, peers)):
+            row = flat[r].numpy()
+            C = [bytes(row[c]) for c in cc]
+            W = [bytes(row[k * (T + 1) + j]) for k in range(nch) for j in yc]
+            y = ys[r].numpy()[:, yc].reshape(-1)
+            tri = self.R.kzg_rlc_host(C, W, y, list(xs), bases, kzg_row_seed(seed, i), self.cfg.host_threads)
+            if not self.R.kzg_check(*tri, *self._kzg_g2):
+                bad.append(w)
+        return {"its": [it], "rows_done": (len(rows_l), bad)}
+
+    def _kzg_rows_step(self, e: dict, must: bool) -> bool:
+        """Advance one per-worker entry: the pairing product of the summed triple once the sums are back, the rows'
+        own products if it fails; True once it is decided and counted."""
+        if "rows_done" not in e:
+            n = len(e["rows"])
+            if e["job"] is None and (must or e["ev"].query()):
+                e["ev"].synchronize()
+                e["job"] = self.R.kzg_check_device_async(e["host"][n].numpy().view(np.uint32), *self._kzg_g2)
+            if not must or e["job"] is None:
+                return False   # (joined only when it must be: the products run on native threads meanwhile)
+            if e["job"].result():
+                e["rows_done"] = (int(e["flags"].sum()), [])
+            else:   # name the culprits: one product per audited row
+                jobs = [(w, self.R.kzg_check_device_async(e["host"][i].numpy().view(np.uint32), *self._kzg_g2))
+                        for i, w in enumerate(e["rows"]) if e["flags"][i]]
+                e["rows_done"] = (len(jobs), [w for w, j in jobs if not j.result()])
+        n, bad = e["rows_done"]
+        it = e["its"][0]
+        self.stats["kzg_checks"] += 1
+        self.stats["kzg_share_checks"] += n
+        if bad:
+            self.stats["kzg_failures"] += 1
+            self.stats["kzg_share_failures"] += len(bad)
+            self.kzg_share_blame += [(it, w) for w in bad]
+            self.log.info("KZG audit (verifySecret per worker) failed in iteration %d for the updates of peers %s",
+                          it, bad)
+        return True
+
+    def _kzg_share_summary(self) -> None:
+        """The run's per-worker counts, logged once per change (drain)."""
+        st = self.stats
+        now = (st["kzg_checks"], st["kzg_share_checks"], st["kzg_share_failures"])
+        if now != getattr(self, "_kzg_share_logged", None):
+            self._kzg_share_logged = now
+            self.log.info("KZG audit (verifySecret per worker): %d blocks, %d worker updates checked, %d failed", *now)
+
     def _kzg_recheck(self, e: dict) -> list:
         """A batch of several rounds failed: check each staged round on its own (device sums +
         pairing, waited for here) and return the iterations that fail individually."""
@@ -129,6 +209,10 @@ class KzgAuditMixin:
         keep = []
         for i, e in enumerate(self._kzg_pending):
             must = final or len(self._kzg_pending) - i > 2
+            if "rows" in e or "rows_done" in e:
+                if not self._kzg_rows_step(e, must):
+                    keep.append(e)
+                continue
             if "ok" not in e and e["job"] is None and (must or e["ev"].query()):
                 e["ev"].synchronize()
                 e["job"] = self.R.kzg_check_device_async(e["host"].numpy().view(np.uint32), *self._kzg_g2)

@@ -29,6 +29,7 @@ class _Rows:
 
     no_commit = False
     qdelta = None   # never the pre-step's rows: the audit sums come from the rows' commitment slots
+    peers = None    # the worker of each row (the per-worker KZG audit names them)
 
     def __init__(self, pts, ys, alive, rows_t, ev):
         self.pts, self.ys, self.alive, self.rows_t, self.ev = pts, ys, alive, rows_t, ev
@@ -86,7 +87,7 @@ class SecAggMixin:
                 self._agg_idx[key] = hit
         return hit
 
-    def _aggregate(self, pts, ys, rowsel, contributing, part, now) -> dict:
+    def _aggregate(self, pts, ys, rowsel, contributing, part, now, peers=None) -> dict:
         """CPU (host crypto) secure aggregation of this rank's kept rows, combined over ranks, then exact recovery;
         GPU rounds aggregate through the native calls (_spec_aggregate_native).
 
@@ -101,9 +102,10 @@ class SecAggMixin:
         cfg, comm = self.cfg, self.comm
         T, nch, pw, pdt = self.T, self.nchunks, self.crypto.point_width, self.crypto.point_dtype
         audit = cfg.audit_aggregate
-        kzg = cfg.kzg_audit != "off"
+        kzg = cfg.kzg_audit in ("consistent", "literal")
         (ccols, wcols, ycols_t, xs_t), xs_list, _, _ = self._agg_index(contributing, part)
         kzg_in = None   # this rank's (commitment sums, witness sums, share sums) for the KZG audit
+        kzg_rows = None   # --kzg-audit shares: this rank's rows themselves (each worker's update on its own)
         ys_part = cs_part = None
         if pts is not None and rowsel:
             flat = pts.view(pts.shape[0], nch * (T + 1), pw)
@@ -114,6 +116,8 @@ class SecAggMixin:
             if kzg:
                 kzg_in = (cs_part, self.crypto.sum_rows(flat[rows_l][:, wcols.long()]),
                           ys_part.index_select(1, ycols_t.long()))
+            if cfg.kzg_audit == "shares":
+                kzg_rows = (flat, ys, rows_l, list(peers) if peers is not None else rows_l, ccols, ycols_t)
         if ys_part is None:   # no local rows: nothing to add
             ys_part = torch.zeros((nch, T), dtype=torch.int64)
         if audit and cs_part is None:   # no local rows: the neutral element (point at infinity)
@@ -141,6 +145,8 @@ class SecAggMixin:
             # each rank audits its own partial aggregate (verifySecret is linear in (C, W, y))
             cs_k, ws_k, y_k = kzg_in
             out["kzg_in"] = (cs_k, ws_k, agg if comm.world == 1 else y_k, xs_t)
+        if kzg_rows is not None:
+            out["kzg_rows"] = kzg_rows
         return out
 
     def _spec_aggregate_native(self, sp, pred, node, amap, flags_set: bool = False, it: int | None = None,
@@ -155,7 +161,8 @@ class SecAggMixin:
         cfg, comm, na = self.cfg, self.comm, self._native
         contributing, part = pred
         (_, _, ycols_t, xs_t), xs_list, _, lid = self._agg_index(contributing, part)
-        kzg = cfg.kzg_audit != "off"
+        kzg = cfg.kzg_audit in ("consistent", "literal")
+        shares = cfg.kzg_audit == "shares"   # the per-worker audit reads the rows in place: no sums of its own
         run_audit = cfg.audit_aggregate
         audit = 1 if (run_audit or kzg) else 0   # the KZG audit reads the commitment sums too
         early = -1
@@ -166,7 +173,7 @@ class SecAggMixin:
                 early, audit = pc.slot, 2   # the audit's sums from the pre-step's chunk commitments, early
             elif sp.no_commit and audit:
                 raise RuntimeError("speculative MSM without commitment slots but no chunk commitments to audit with")
-        if kzg and getattr(self, "_kzg_copied", None) is not None:
+        if (kzg or shares) and getattr(self, "_kzg_copied", None) is not None:
             S.current().wait_event(self._kzg_copied)   # the last aggregate's copies before its buffers are rewritten
         # it: the round being aggregated (default: the FSM's, begun); W: the model it starts from (default: the engine's)
         # -- a speculative front passes both, ahead of the previous block's commit (engine._spec_front_launch)
@@ -209,6 +216,8 @@ class SecAggMixin:
         if kzg:
             out["kzg_in"] = self._kzg_capture(lid, ycols_t, xs_t)
             out["kzg_events"] = [self._kzg_copied]   # the audit stream reads the copies (_kzg_adopt)
+        elif shares and sp is not None:
+            out["kzg_rows"] = self._kzg_rows_capture(sp, ycols_t, xs_t, it)
         return out
 
     def _kzg_capture(self, lid: int, ycols_t, xs_t):
@@ -236,7 +245,37 @@ class SecAggMixin:
             self._kzg_copied = S.record(st)
         return cs, ws, ys, xs_t
 
-    def _native_rows_aggregate(self, pts, ys, rowsel: list, pred, ev) -> dict:
+    def _kzg_rows_capture(self, sp, ycols_t, xs_t, it: int):
+        """--kzg-audit shares: the per-worker sums over the rows the aggregation has just read (sp.pts / sp.ys in place,
+        the rows' flags as the selection set them), queued on the audit stream behind the streams that wrote them;
+        only the [n + 1, 3, 24] result comes back.  The flags are copied first, on a stream of their own (a pre-step
+        sets the slot's flags again two rounds on; the next aggregation waits for the copy, _kzg_copied), and the
+        speculative MSM waits for the kernel before it rewrites the slot (NativeSecAgg.slot_guards)."""
+        st = self.__dict__.get("kzg_stream")
+        if st is None:
+            st = self.kzg_stream = torch.cuda.Stream(device=self.dev, priority=torch.cuda.Stream.priority_range()[0])
+            self._kzg_flag_stream = torch.cuda.Stream(device=self.dev)
+        fs = self._kzg_flag_stream
+        for src in (S.current(), self.side_stream, self.upload_stream, self.witness_stream):
+            S.wait(fs, src)
+        if sp.ev is not None:
+            fs.wait_event(sp.ev)
+        with S.use(fs):
+            alive = sp.alive.clone()
+            self._kzg_copied = S.record(fs)
+        st.wait_event(self._kzg_copied)
+        peers = getattr(sp, "peers", None) or [self.lo + r for r in sp.rows]
+        for t in (sp.pts, sp.ys, alive):
+            t.record_stream(st)
+        with S.use(st):
+            e = self._kzg_rows_launch(sp.pts, sp.ys, alive, ycols_t, xs_t, peers, it)
+        na, p = self._native, sp.pts.data_ptr()
+        ring = na.__dict__.get("_spec_ring") if na is not None else None
+        if ring is not None and any(sl["pts"].data_ptr() == p for sl in ring["slots"]):
+            na.slot_guards[p] = e["ev"]
+        return e
+
+    def _native_rows_aggregate(self, pts, ys, rowsel: list, pred, ev, peers=None) -> dict:
         """The host-decided path's GPU aggregation (no device selection, a speculative miss, a prediction mismatch):
         rows `rowsel` of the share tensors pts / ys (None: no local rows) through the same native calls, with the
         rows' flags set here instead of by the selection kernel."""
@@ -246,6 +285,10 @@ class SecAggMixin:
             keep[np.asarray(rowsel, np.int64)] = 1
             rows = _Rows(pts, ys, h2d(keep, torch.int32, self.dev),
                          h2d(np.arange(pts.shape[0], dtype=np.int32), torch.int32, self.dev), ev)
+            if peers is not None:   # rowsel[i] is worker peers[i]'s row
+                rows.peers = [None] * pts.shape[0]
+                for r, w in zip(rowsel, peers):
+                    rows.peers[r] = w
         return self._spec_aggregate_native(rows, pred, None, None, flags_set=True)
 
     # ------------------------------------------------------------------ read-backs and the audit
@@ -314,9 +357,10 @@ class SecAggMixin:
                     ev = S.record() if self.gpu else None
         with tm.phase("recover"):
             if self.gpu:
-                agg = self._native_rows_aggregate(pts, ys, rowsel, (contributing, part_of), ev)
+                agg = self._native_rows_aggregate(pts, ys, rowsel, (contributing, part_of), ev, peers=local_used)
             else:
-                agg = self._aggregate(pts, ys, rowsel, contributing, part_of, self._now(plan.iteration))
+                agg = self._aggregate(pts, ys, rowsel, contributing, part_of, self._now(plan.iteration),
+                                      peers=local_used)
             return self._finish_secagg(plan, node_list, commit_of, agg)
 
     def _spec_topup(self, spec, local_used: list, row_of: dict, qdelta):
@@ -338,6 +382,7 @@ class SecAggMixin:
             return None
         S.current().wait_event(sp2.ev)   # the slot's flags and the new rows before the aggregation reads them
         self.stats["spec_topups"] = self.stats.get("spec_topups", 0) + 1
+        sp2.peers = list(spec[0]) + [w for w in local_used if w not in have]
         return sp2
 
     def _finish_secagg(self, plan, node_list, commit_of, h):

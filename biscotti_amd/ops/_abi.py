@@ -43,6 +43,10 @@ SIGNATURES = {
     "bsc_vrf_prove": [P, P, P, P, I, I, P, P, P, P, P],
     "bsc_vrf_prove_p": [P, P, P, P, I, I, P, P, P, P, I, P],
     "bsc_vrf_verify": [P, I, P, P, P, I, I, P, P, P, P, P, P, P, P, I, P],
+    # schnorr.hip
+    "bsc_schnorr_verify": [P, P, P, P, P, I, I, I, P, P, P],
+    "bsc_schnorr_challenge": [P, P, I, P, P, P],
+    "bsc_schnorr_point": [P, P, P, P, I, I, P, P],
     # kzg.hip
     "bsc_kzg_blocks": [I, I],
     "bsc_kzg_rlc": [P, P, P, P, I, I, I, P, I, I, U64, P, P, P],

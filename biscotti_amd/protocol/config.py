@@ -13,7 +13,6 @@ class RunConfig:
     node_index: int = -1            # -i  (per-process mode; SPMD runs host several peers per rank)
     dataset: str = "mnist"          # -d  mnist | creditcard
     peers_file: str | None = None   # -f
-    my_ip: str = ""                 # -a
     port: str = ""                  # -p
     colluders: int = 0              # -c  percent
     num_miners: int = 3             # -na
@@ -82,6 +81,13 @@ class RunConfig:
     #                                 (status 5); host proofs (the run's last round, --no-vrf-device, no GPU)
     #                                 with the host verifier.  drain() sets stats vrf_audit_checked /
     #                                 vrf_audit_failures; failures are logged once, never change the chain
+    sig_audit: bool = False         # verify every signature this rank's verifiers produce (not in the reference),
+    #                                 where their batch is joined: item (v, j) is sig[v, j] over the commitment of
+    #                                 worker inboxes[v][j] under pk[v], accepted slots only.  GPU: one launch of
+    #                                 k_schnorr_verify (kernels/schnorr.hip) per batch on a side stream into a
+    #                                 device counter, nothing read before drain(); CPU, or status 3: the host
+    #                                 verifier.  drain() sets stats sig_audit_checked / sig_audit_failures;
+    #                                 failures are logged once, never change the chain; no collective is added
     kzg_audit: str = "off"          # batched verifySecret (kyber.go:650-673) over every (chunk, share point) of
     #                                 the aggregate: off | consistent (y against PK[poly*k]) | literal (y
     #                                 against G1: the reference's formula, which only chunk 0 satisfies, Q9).
@@ -268,7 +274,7 @@ def add_reference_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("-i", dest="node_index", type=int, default=-1, help="this node's index")
     ap.add_argument("-d", dest="dataset", default="mnist", help="dataset (mnist | creditcard)")
     ap.add_argument("-f", dest="peers_file", default=None, help="peers file (IP:port per line)")
-    ap.add_argument("-a", dest="my_ip", default="", help="public IP")
+    ap.add_argument("-a", dest="my_ip", default="", help="public IP (accepted, never read: no field)")
     ap.add_argument("-pa", dest="my_private_ip", default="", help="private IP (accepted, never read: no field)")
     ap.add_argument("-p", dest="port", default="", help="port")
     ap.add_argument("-c", dest="colluders", type=int, default=0, help="colluders (percent)")
@@ -319,6 +325,9 @@ def add_framework_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--vrf-audit", dest="vrf_audit", action="store_true",
                     help="verify every VRF proof this rank produces (device batches in place, K16); failures "
                          "are counted and logged, never change the chain")
+    ap.add_argument("--sig-audit", dest="sig_audit", action="store_true",
+                    help="verify every signature this rank's verifiers produce (k_schnorr_verify on a GPU, K14); "
+                         "failures are counted and logged, never change the chain")
     ap.add_argument("--kzg-audit", default="off", choices=["off", "consistent", "literal", "shares"],
                     help="batched verifySecret over each round's aggregate (K13)")
     ap.add_argument("--comm-timeout", dest="comm_timeout_s", type=float, default=300.0)

@@ -47,6 +47,7 @@ from .head import PlanView, RoundHeadMixin
 from .kzg_audit import KzgAuditMixin
 from .secagg import SecAggMixin
 from .verify import VerifyMixin
+from .sig_audit import SigAuditMixin
 from .vrf_audit import VrfAuditMixin
 
 SIDE_STREAM_SKIP_EVERY = 4   # the speculative-MSM stream leaves every 4th CU to the critical path
@@ -75,7 +76,8 @@ class RoundResult:
     approved_by_krum: list = field(default_factory=list)  # updates at least one verifier accepted
 
 
-class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, VrfAuditMixin, FaultsMixin):
+class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, VrfAuditMixin, SigAuditMixin,
+                     FaultsMixin):
     def __init__(self, cfg: RunConfig, comm: Comm | None = None):
         cfg.validate()
         self.cfg = cfg
@@ -226,6 +228,7 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
                       "native_collectives": int(self._native_comm)}
         self._kzg_init(cfg)
         self._vrf_audit_init(cfg)
+        self._sig_audit_init(cfg)
         self._churn = {"down": {}, "view": {}, "epoch": {}, "acc": 0.0, "kills": 0, "rejoins": 0,
                        "synced_blocks": 0}
         self.stats["churn"] = self._churn
@@ -354,6 +357,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
             joins, self._sign_joins = self._sign_joins, []
             for join in joins:
                 join()
+            if self.cfg.sig_audit:   # after the last signature batches have been joined (and audited)
+                self._sig_audit_finish()
             t3 = time.perf_counter()
             self._resolve_evals()
             # where a final drain's time goes (bench reports it next to drain_ms)
@@ -411,6 +416,7 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
             # the HBM-resident tables (up to ~90 GB) go now, not whenever the engine is collected
             if isinstance(self.crypto, DeviceCrypto):
                 self.crypto.eng.release()
+            self._sig_release()
             if self._native is not None:
                 self._native.close()
                 self._native = None

@@ -303,17 +303,63 @@ class SecAggMixin:
         ok = self.crypto.check_aggregate(coeffs.cpu(), csum.cpu())
         return lambda: ok
 
+    # ------------------------------------------------------------------ --verify-signatures (Q5)
+    def _sig_filter(self, plan, approved: list, commit_of, signatures: dict) -> list:
+        """The approved workers with at least len(plan.verifiers) // 2 signatures valid under some verifier's key
+        (main.go:269-277, Q5).  One item per (approved worker w, signature of w, verifier v of the plan) over the
+        message commit_of[w].  GPU: one launch of k_schnorr_verify and one read-back on a stream of its own
+        (sig_audit.py _sig_verifier owns the tables); the CPU engine, and engine.sig_dev_off = True, run the host
+        loop: the same rule, the same list.  Stats: sig_checks (items), sig_failures (signatures valid under no
+        key).  Test seams: engine.sig_dev_off; engine.sig_tamper, a callable applied to the `signatures` dict before
+        the check (it returns the dict to check, or None after changing it in place)."""
+        R = self.R
+        need = len(plan.verifiers) // 2
+        tamper = getattr(self, "sig_tamper", None)
+        if tamper is not None:
+            got = tamper(signatures)
+            signatures = signatures if got is None else got
+        vs = list(plan.verifiers)
+        sigs_of = {w: list(signatures.get(w, [])) for w in approved}
+        msgs = {w: commit_of[w] for w in approved}
+        nsig = sum(len(s) for s in sigs_of.values())
+        self.stats["sig_checks"] = self.stats.get("sig_checks", 0) + nsig * len(vs)
+        device = (self.gpu and not getattr(self, "sig_dev_off", False) and nsig > 0 and vs
+                  and all(len(m) == 64 for m in msgs.values()))
+        if not device:
+            good = {w: sum(any(R.schnorr_verify(msgs[w], self.pk[v], sg) for v in vs) for sg in sigs_of[w])
+                    for w in approved}
+        else:
+            from ..ops.schnorr import quorum
+
+            sv = self._sig_verifier()
+            mi, ki, sg_rows, groups = [], [], [], []
+            for m, w in enumerate(approved):
+                for s, sg in enumerate(sigs_of[w]):
+                    if len(sg) != 64:       # the host verifier rejects it under every key
+                        continue
+                    for v in vs:
+                        mi.append(m)
+                        ki.append(v)
+                        sg_rows.append(sg)
+                        groups.append((w, s))
+            good = {w: 0 for w in approved}
+            if sg_rows:
+                with S.use(self._sig_stream):
+                    wait = sv.verify_resolved(np.frombuffer(b"".join(msgs[w] for w in approved), np.uint8),
+                                              mi, ki, np.frombuffer(b"".join(sg_rows), np.uint8))
+                good.update(quorum(wait(), groups))
+        self.stats["sig_failures"] = self.stats.get("sig_failures", 0) + nsig - sum(good.values())
+        return [w for w in approved if good[w] >= need]
+
     # ------------------------------------------------------------------ secure aggregation path
     def _secure_aggregation(self, plan, live, approved, qdelta, local_workers, row_of, commit_of,
                             signatures, spec=None, sa=None):
         cfg, R, fsm, tm = self.cfg, self.R, self.fsm, self.timer
         self._last_nodes = []
         if cfg.verify_signatures and cfg.verification:
-            # miners reject shares without >= nv/2 valid verifier signatures (main.go:269-277, Q5)
-            need = len(plan.verifiers) // 2
-            approved = [w for w in approved
-                        if sum(any(R.schnorr_verify(commit_of[w], self.pk[v], sg) for v in plan.verifiers)
-                               for sg in signatures.get(w, [])) >= need]
+            # miners reject shares without >= nv/2 valid verifier signatures (main.go:269-277, Q5): on a GPU one
+            # launch of the batched verifier and one read-back, else the host loop (_sig_filter)
+            approved = self._sig_filter(plan, approved, commit_of, signatures)
         with tm.phase("shares"):
             # share routing + the leader's view natively (the routes never cross into Python)
             online, quorum, node_list, contributing, part_of = fsm.route_view(approved)

@@ -534,12 +534,19 @@ class VerifyMixin:
                             # the commitments are still the pre-step's Jacobian rows: the job marshals the signed
                             # ones on its own thread (the round's thread skips the table's ~30 us marshal)
                             S.host_wait(jac[1])
-                            sign["job"] = R.schnorr_sign_rows_jac_async(jac[0].numpy().view(np.uint32),
-                                                                        rmap[ws].tolist(), sks, kk.tolist(), bases,
-                                                                        ws.tolist(), threads, after_vrf)
+                            jrows = jac[0].numpy().view(np.uint32)
+                            sign["job"] = R.schnorr_sign_rows_jac_async(jrows, rmap[ws].tolist(), sks, kk.tolist(),
+                                                                        bases, ws.tolist(), threads, after_vrf)
+                            if cfg.sig_audit:   # the signed messages, read where the signer reads them: a deferred
+                                #                 join comes after the pinned rows have moved on to a later round
+                                sign["msgs"] = R.g1_marshal_jac_batch(np.ascontiguousarray(jrows[rmap[ws]]))
+                                sign["pks"] = [self.pk[local_vs[k]] for k in kk.tolist()]
                         else:
                             sign["job"] = R.schnorr_sign_rows_async(commit_of.table, rmap[ws].tolist(), sks,
                                                                     kk.tolist(), bases, ws.tolist(), threads, after_vrf)
+                            if cfg.sig_audit:
+                                sign["msgs"] = np.ascontiguousarray(commit_of.table[rmap[ws]])
+                                sign["pks"] = [self.pk[local_vs[k]] for k in kk.tolist()]
                 sign["prep"] = _prep_sign
                 if defer_sign:   # prepared in the next round's VRF wait, started once its outputs are known
                     self._pre_vrf_work.append(_prep_sign)
@@ -555,6 +562,8 @@ class VerifyMixin:
                         sl_v, sl_j = sign["sl"]
                         sig_np[sl_v, sl_j] = sign["job"].result_array()
                     self.last_signatures = sig_np   # [nv, ni, 64]: this rank's verifiers' signatures
+                    if cfg.sig_audit:   # every signature of this batch, under its verifier's key (sig_audit.py)
+                        self._sig_audit_batch(sig_np, sign["sl"], sign.get("msgs"), sign.get("pks"), plan, inboxes, it)
                     # the signatures travel to the workers (and on to the miners) only where a consumer
                     # reads them: plain blocks carry them, --verify-signatures checks them; on the secure
                     # path each rank keeps the ones its verifiers produced (Q5) as this matrix

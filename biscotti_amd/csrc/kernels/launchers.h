@@ -18,15 +18,13 @@ int bsc_shares_msm_ka(const long long* coeffs, int d, const int* rows_host, int 
                       int group_rows, uint32_t* out_pts, long long* out_y, void* stream);
 int bsc_set_alive(const int* accept, const int* src, int n, int* alive, void* stream);
 int bsc_sum_rows2(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols, int ncols,
-                  const int* row_mask, uint32_t* out, void* stream);
-int bsc_sum_rows2_pos(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols, int ncols,
-                      const int* row_mask, uint32_t* out, void* stream);
+                  const int* row_mask, int mask_by_pos, uint32_t* out, void* stream);
 int bsc_sum_cols_serial(const uint32_t* pts, int ncols_in, int nrows, const int* cols, int ncols,
                         const int* row_mask, uint32_t* out, void* stream);
-int bsc_segment_sum_h(const uint32_t* pts, int ngroups, int n, int stride, int off, uint32_t* out, uint32_t* hout,
-                      void* stream);
-int bsc_chunk_check_h(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
-                      const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream);
+int bsc_segment_sum(const uint32_t* pts, int ngroups, int n, int stride, int off, uint32_t* out, uint32_t* hout,
+                    void* stream);
+int bsc_chunk_check(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
+                    const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream);
 int bsc_g1_unmarshal(const uint8_t* in, int n, const int* pre, uint32_t* out, int* valid, void* stream);
 int bsc_chain_audit(const double* models, const int* kind, const int* offsets, int L, int d, const double* plain,
                     const int* pbeg, const int* pend, int np, const uint8_t* commits, const int* len_ok, int n,
@@ -35,12 +33,10 @@ int bsc_chain_audit(const double* models, const int* kind, const int* offsets, i
                     int* res, int* h_res, void* stream);
 int bsc_wave_prio_msm(int on);
 // ml.hip
-int bsc_softmax_step_ones(const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,
-                          const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed, int iteration,
-                          float max_norm, double qscale, float* delta, long long* qdelta, float* loss, int lo,
-                          int* ones, int nones, void* stream);
-int bsc_gram_stacked(const float* X, int U1, const float* X2, int U2, long long stride2, int D, int kchunk,
-                     double* part, double* gram, unsigned int* count, const double* nn, void* stream);
+int bsc_softmax_step(const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,
+                     const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed, int iteration,
+                     float max_norm, double qscale, float* delta, long long* qdelta, float* loss, int lo, int* ones,
+                     int nones, void* stream);
 int bsc_gram_stacked_range(const float* X, int U1, const float* X2, int U2, long long stride2, int D, int kchunk,
                            int p0, int p1, double* part, double* gram, unsigned int* count, const double* nn,
                            void* stream);

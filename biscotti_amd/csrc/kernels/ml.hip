@@ -1526,23 +1526,15 @@ extern "C" int bsc_sum_rows_i64_tail(const long long* ys, int R, long long C, co
   return (int)hipGetLastError();
 }
 
-extern "C" int bsc_softmax_step_ones(const float* X, const int* y, const long long* off, const int* ntrain,
-                                     const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
-                                     unsigned long long seed, int iteration, float max_norm, double qscale, float* delta,
-                                     long long* qdelta, float* loss, int lo, int* ones, int nones, void* stream) {
+extern "C" int bsc_softmax_step(const float* X, const int* y, const long long* off, const int* ntrain,
+                                const int* pid, const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed,
+                                int iteration, float max_norm, double qscale, float* delta, long long* qdelta,
+                                float* loss, int lo, int* ones, int nones, void* stream) {
   if (D_IN <= 0 || D_OUT > 16 || B > 16) return -1;
   if (P <= 0) return 0;
   hipLaunchKernelGGL(k_softmax_step, dim3(P), dim3(SM_THREADS), 0, (hipStream_t)stream, X, y, off, ntrain, pid, W, D_IN,
                      D_OUT, B, P, seed, iteration, max_norm, qscale, delta, qdelta, loss, lo, ones, nones);
   return (int)hipGetLastError();
-}
-
-extern "C" int bsc_softmax_step(const float* X, const int* y, const long long* off, const int* ntrain,
-                                const int* pid, const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed,
-                                int iteration, float max_norm, double qscale, float* delta, long long* qdelta,
-                                float* loss, int lo, void* stream) {
-  return bsc_softmax_step_ones(X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, delta,
-                               qdelta, loss, lo, nullptr, 0, stream);
 }
 
 extern "C" int bsc_logreg_step(const double* X, const double* y, const long long* off, const int* nrows,
@@ -1630,10 +1622,6 @@ extern "C" int bsc_gram_stacked_range(const float* X, int U1, const float* X2, i
                      T, (U1 + 15) / 16, nn != nullptr ? 1 : 0);
   return (int)hipGetLastError();
 }
-extern "C" int bsc_gram_stacked(const float* X, int U1, const float* X2, int U2, long long stride2, int D, int kchunk,
-                                double* part, double* gram, unsigned int* count, const double* nn, void* stream) {
-  return bsc_gram_stacked_range(X, U1, X2, U2, stride2, D, kchunk, 0, 0, part, gram, count, nn, stream);
-}
 namespace {
 // the noise-aware committee Krum on a finished stacked Gram: rows kernel, then the vote.  nz / sc [U1][nn] are
 // device arrays, or (host_tabs) host arrays that travel in the rows kernel's argument block -- which holds
@@ -1688,23 +1676,18 @@ extern "C" int bsc_krum_committee_noise_ka(const double* gram, int U1, int U, co
   return krum_committee_noise_any(gram, U1, U, nz_host, sc_host, true, nn, inbox, V, n, groupsize, n_accept, need,
                                   lead_rank, cap, scores, acc, node, ws, h_out, amap, nspec, alive, stream);
 }
-extern "C" int bsc_eval_error(const float* X, const int* y, int N, int D_IN, int D_OUT, const double* W,
-                              int transform, int split, unsigned int* err, void* stream) {
-  if (D_OUT > 16 || D_IN <= 0) return -1;
-  if (N <= 0) return 0;
-  const int tiles = (N + 15) / 16;
-  hipLaunchKernelGGL(k_eval_error, dim3(tiles), dim3(256), 0, (hipStream_t)stream, X, y, N, D_IN, D_OUT, W,
-                     transform, split, err);
-  return (int)hipGetLastError();
-}
-
 // the evaluation with its accumulator reset and its read-back into pinned memory in one call (the engine
 // queues it every round; three Python-level stream operations cost more host time than the kernel)
 extern "C" int bsc_eval_error_rb(const float* X, const int* y, int N, int D_IN, int D_OUT, const double* W,
                                  int transform, int split, unsigned int* err, unsigned int* err_host, void* stream) {
   if (hipMemsetAsync(err, 0, 2 * sizeof(unsigned int), (hipStream_t)stream) != hipSuccess) return -1;
-  const int rc = bsc_eval_error(X, y, N, D_IN, D_OUT, W, transform, split, err, stream);
-  if (rc != 0) return rc;
+  if (D_OUT > 16 || D_IN <= 0) return -1;
+  if (N > 0) {
+    hipLaunchKernelGGL(k_eval_error, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream, X, y, N, D_IN, D_OUT, W,
+                       transform, split, err);
+    const int rc = (int)hipGetLastError();
+    if (rc != 0) return rc;
+  }
   return (int)hipMemcpyAsync(err_host, err, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, (hipStream_t)stream);
 }
 
@@ -1807,16 +1790,6 @@ extern "C" int bsc_recover_w_clock(const long long* ys, int nrows, long long rst
                      T, mask, ycols, xs, npts, A, basis, poly, shift, inv_lo, inv_hi, d, W, qscale, W_new, coeffs,
                      status, agg_out, h_W, h_status, h_clock);
   return (int)hipGetLastError();
-}
-
-// a dense [nrows][nch][T] tensor, no host mirrors
-extern "C" int bsc_recover_w(const long long* ys, int nrows, int nch, int T, const int* mask, const int* ycols,
-                             const int* xs, int npts, const long long* A, const int* basis, int poly, int shift,
-                             unsigned long long inv_lo, unsigned long long inv_hi, int d, const double* W, double qscale,
-                             double* W_new, long long* coeffs, int* status, long long* agg_out, void* stream) {
-  return bsc_recover_w_clock(ys, nrows, (long long)nch * T, nch, T, mask, ycols, xs, npts, A, basis, poly, shift,
-                             inv_lo, inv_hi, d, W, qscale, W_new, coeffs, status, agg_out, nullptr, nullptr, nullptr,
-                             stream);
 }
 
 extern "C" int bsc_add_rows(const float* delta, int D, const int* rows, int nrows, const double* W, double* W_new,

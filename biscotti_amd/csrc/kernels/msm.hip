@@ -437,9 +437,8 @@ __device__ __forceinline__ jac aff_add_aff(const aff& p, const aff& q) {
 extern "C" __global__ void __launch_bounds__(64) k_chunk_check(const long long* coeffs, int d, int poly,
                                                               const uint32_t* tbl_pk, int B0, int NW,
                                                               const uint32_t* csum, int nm, int nch, int* ok,
-                                                              int* h_ok, int low) {
-  if (low) BSC_SET_PRIO(BSC_PRIO_AHEAD);   // bsc_set_side_prio: below the speculative MSM
-  else BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+                                                              int* h_ok) {
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
   __shared__ uint32_t sh[64 * 24];
   __shared__ int dig[16][9];      // signed digit of (coefficient j, window w); NW <= 9 (bsc_chunk_check)
   __shared__ uint32_t items[16 * 9];   // nonzero digits: table entry | sign bit
@@ -505,24 +504,10 @@ extern "C" __global__ void __launch_bounds__(64) k_chunk_check(const long long* 
 }
 
 // ------------------------------------------------------------------ reductions
-// out[i] = sum_{r < nrows} pts[(rows[r] * ncols_in + cols[i]) * 24]   (cols == nullptr: cols[i] = i)
-// One thread per output column; used for miner-side share aggregation (aggregateSecret).
-extern "C" __global__ void __launch_bounds__(128) k_sum_rows(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols,
-                                      int ncols, uint32_t* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ncols) return;
-  const int col = cols ? cols[i] : i;
-  jac acc = jac_inf();
-  for (int r = 0; r < nrows; ++r) {
-    const int row = rows ? rows[r] : r;
-    acc = jac_add(acc, ld_jac(pts + 24 * ((size_t)row * ncols_in + col)));
-  }
-  st_jac(out + 24 * (size_t)i, acc);
-}
-
-// Two-level version: block = 32 columns x 8 row groups; each thread sums every 8th row of its
-// column, then an LDS tree over the 8 partials.  8x the parallelism of k_sum_rows, and the column
-// list may concatenate several miners' slots (one launch per rank).
+// out[i] = sum_{r < nrows} pts[(rows[r] * ncols_in + cols[i]) * 24]   (cols == nullptr: cols[i] = i;
+// rows == nullptr: rows[r] = r).  Used for miner-side share aggregation (aggregateSecret).
+// Two-level: each thread sums every 16th row of its column, then an LDS tree over the 16 partials.  The
+// column list may concatenate several miners' slots (one launch per rank).
 // row_mask (optional, indexed by input row, or by position r in `rows` when mask_by_pos): rows whose
 // flag is 0 are left out -- the device-side selection of the approved workers' shares, decided by the
 // verification kernels on the GPU.
@@ -583,11 +568,9 @@ extern "C" __global__ void __launch_bounds__(256) k_sum_cols_serial(const uint32
 // Sum of a strided segment per group: out[g] = sum_{k<n} pts[(g*n + k)*stride + off], one block
 // per group, LDS tree.  Used for the full commitment = sum of chunk commitments.
 extern "C" __global__ void __launch_bounds__(256) k_segment_sum(const uint32_t* pts, int n, int stride, int off,
-                                                               uint32_t* out, uint32_t* hout, int low) {
-  // the full commitments: the round's block build waits for them (a latency chain) -- or, bsc_set_side_prio, below
-  // the speculative MSM they run beside (the next block build is a round away)
-  if (low) BSC_SET_PRIO(BSC_PRIO_AHEAD);
-  else BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+                                                               uint32_t* out, uint32_t* hout) {
+  // the full commitments: the round's block build waits for them (a latency chain)
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
   __shared__ uint32_t sh[256 * 24];
   const int g = blockIdx.x;
   jac acc = jac_inf();
@@ -917,44 +900,21 @@ extern "C" int bsc_set_alive(const int* accept, const int* src, int n, int* aliv
   return (int)hipGetLastError();
 }
 
-extern "C" int bsc_sum_rows(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols, int ncols,
-                            uint32_t* out, void* stream) {
-  if (ncols <= 0) return 0;
-  hipLaunchKernelGGL(k_sum_rows, dim3(blocks_for(ncols, 128)), dim3(128), 0, (hipStream_t)stream, pts, ncols_in,
-                     rows, nrows, cols, ncols, out);
-  return (int)hipGetLastError();
-}
-
+// row_mask (nullable) is indexed by the input row, or -- mask_by_pos -- by the position in `rows` (a mask over a
+// row list, e.g. the speculative MSM's alive flags applied to the pre-step's per-peer chunk commitments)
 extern "C" int bsc_sum_rows2(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols,
-                             int ncols, const int* row_mask, uint32_t* out, void* stream) {
+                             int ncols, const int* row_mask, int mask_by_pos, uint32_t* out, void* stream) {
   if (ncols <= 0) return 0;
   hipLaunchKernelGGL(k_sum_rows2, dim3(blocks_for(ncols, 16)), dim3(256), 0, (hipStream_t)stream, pts, ncols_in,
-                     rows, nrows, cols, ncols, row_mask, 0, out);
+                     rows, nrows, cols, ncols, row_mask, mask_by_pos ? 1 : 0, out);
   return (int)hipGetLastError();
-}
-
-static int g_wit_tree = 0;   // bsc_set_witness_tree(1): the witness sums in the LDS-tree form (A/Bs)
-extern "C" int bsc_set_witness_tree(int on) {
-  g_wit_tree = on ? 1 : 0;
-  return 0;
 }
 
 extern "C" int bsc_sum_cols_serial(const uint32_t* pts, int ncols_in, int nrows, const int* cols, int ncols,
                                    const int* row_mask, uint32_t* out, void* stream) {
   if (ncols <= 0) return 0;
-  if (g_wit_tree) return bsc_sum_rows2(pts, ncols_in, nullptr, nrows, cols, ncols, row_mask, out, stream);
   hipLaunchKernelGGL(k_sum_cols_serial, dim3(blocks_for(ncols, 256)), dim3(256), 0, (hipStream_t)stream, pts, ncols_in,
                      nrows, cols, ncols, row_mask, out);
-  return (int)hipGetLastError();
-}
-
-// the same with row_mask indexed by the position in `rows` (a mask over a row list, e.g. the speculative
-// MSM's alive flags applied to the pre-step's per-peer chunk commitments)
-extern "C" int bsc_sum_rows2_pos(const uint32_t* pts, int ncols_in, const int* rows, int nrows, const int* cols,
-                                 int ncols, const int* row_mask, uint32_t* out, void* stream) {
-  if (ncols <= 0) return 0;
-  hipLaunchKernelGGL(k_sum_rows2, dim3(blocks_for(ncols, 16)), dim3(256), 0, (hipStream_t)stream, pts, ncols_in,
-                     rows, nrows, cols, ncols, row_mask, 1, out);
   return (int)hipGetLastError();
 }
 
@@ -968,44 +928,27 @@ extern "C" int bsc_commit_rows(const long long* coeffs, int d, const int* rows, 
   hipLaunchKernelGGL(k_commit_rows, dim3(nrows * nslab), dim3(256), 0, (hipStream_t)stream, coeffs, d, rows, nrows,
                      tbl_pk, B0, NW, partial);
   hipLaunchKernelGGL(k_segment_sum, dim3(nrows), dim3(256), 0, (hipStream_t)stream, partial, nslab, 1, 0, out,
-                     (uint32_t*)nullptr, 0);
+                     (uint32_t*)nullptr);
   return (int)hipGetLastError();
-}
-
-// the round's side reductions (the pre-step's full-commitment sums, the aggregate audit) at the critical class
-// (default) or one below the speculative share MSM (1): experiments and A/Bs (RunConfig ablation side_prio_low)
-static int g_side_low = 0;
-extern "C" int bsc_set_side_prio(int low) {
-  g_side_low = low ? 1 : 0;
-  return 0;
 }
 
 // hout (nullable): pinned host mirror of out
-extern "C" int bsc_segment_sum_h(const uint32_t* pts, int ngroups, int n, int stride, int off, uint32_t* out,
-                                 uint32_t* hout, void* stream) {
-  if (ngroups <= 0) return 0;
-  hipLaunchKernelGGL(k_segment_sum, dim3(ngroups), dim3(256), 0, (hipStream_t)stream, pts, n, stride, off, out, hout,
-                     g_side_low);
-  return (int)hipGetLastError();
-}
 extern "C" int bsc_segment_sum(const uint32_t* pts, int ngroups, int n, int stride, int off, uint32_t* out,
-                               void* stream) {
-  return bsc_segment_sum_h(pts, ngroups, n, stride, off, out, nullptr, stream);
+                               uint32_t* hout, void* stream) {
+  if (ngroups <= 0) return 0;
+  hipLaunchKernelGGL(k_segment_sum, dim3(ngroups), dim3(256), 0, (hipStream_t)stream, pts, n, stride, off, out, hout);
+  return (int)hipGetLastError();
 }
 
 // h_ok (nullable): pinned host mirror of ok
-extern "C" int bsc_chunk_check_h(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
-                                 const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream) {
+extern "C" int bsc_chunk_check(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
+                               const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream) {
   if (nch <= 0 || nm <= 0) return 0;
   if (poly < 1 || poly > 16 || nm > 64 || B0 < 8 || B0 > 20 || B0 + 8 * (NW - 1) < 65 || NW > 9) return -1;
   if ((long long)nch * poly < d || (long long)(nch - 1) * poly >= d) return -1;
   hipLaunchKernelGGL(k_chunk_check, dim3(nch), dim3(64), 0, (hipStream_t)stream, coeffs, d, poly, tbl_pk, B0, NW,
-                     csum, nm, nch, ok, h_ok, g_side_low);
+                     csum, nm, nch, ok, h_ok);
   return (int)hipGetLastError();
-}
-extern "C" int bsc_chunk_check(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
-                               const uint32_t* csum, int nm, int nch, int* ok, void* stream) {
-  return bsc_chunk_check_h(coeffs, d, poly, tbl_pk, B0, NW, csum, nm, nch, ok, nullptr, stream);
 }
 
 extern "C" int bsc_marshal(const uint32_t* pts, int n, uint8_t* out, void* stream) {

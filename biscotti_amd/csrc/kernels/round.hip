@@ -226,7 +226,7 @@ int secagg(RoundCtx* c, const Layout& L, const uint32_t* pts, int R, const long 
   RC_CHECK(hipEventRecord(c->ev_main, c->main));
   if (audit == 1) {
     RC_CHECK(hipStreamWaitEvent(c->side, c->ev_main, 0));
-    RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, L.ccols, c->nch, mask, c->cs, c->side));
+    RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, L.ccols, c->nch, mask, 0, c->cs, c->side));
     RC_CHECK(hipEventRecord(c->ev_side, c->side));
   }
   RC_CHECK(hipStreamWaitEvent(c->wit, c->ev_main, 0));
@@ -247,8 +247,8 @@ extern "C" int bsc_round_audit(void* ctx, const long long* coeffs, const uint32_
   if (c == nullptr) return -1;
   c->aud_k ^= 1;
   RC_CHECK(hipStreamWaitEvent(c->main, c->ev_side, 0));
-  RC_CHECK(bsc_chunk_check_h(coeffs, c->d, c->poly, c->tbl_pk, c->b0, c->nw, cs, 1, c->nch, ok,
-                             h_ok + (size_t)c->aud_k * c->nch, c->main));
+  RC_CHECK(bsc_chunk_check(coeffs, c->d, c->poly, c->tbl_pk, c->b0, c->nw, cs, 1, c->nch, ok,
+                           h_ok + (size_t)c->aud_k * c->nch, c->main));
   RC_CHECK(hipEventRecord(c->aud_k ? c->ev_audit1 : c->ev_audit, c->main));
   return 0;
 }
@@ -273,7 +273,7 @@ static int csum_early(RoundCtx* c, const PreSlot& p, const int* rows, int R, con
   RC_CHECK(hipEventRecord(c->ev_main, c->main));
   RC_CHECK(hipStreamWaitEvent(st, c->ev_main, 0));
   if (p.ev_ccom != nullptr) RC_CHECK(hipStreamWaitEvent(st, p.ev_ccom, 0));
-  RC_CHECK(bsc_sum_rows2_pos(p.ccom, c->nch, rows, R, nullptr, c->nch, mask, cs, st));
+  RC_CHECK(bsc_sum_rows2(p.ccom, c->nch, rows, R, nullptr, c->nch, mask, 1, cs, st));
   RC_CHECK(hipEventRecord(c->ev_side, st));
   return 0;
 }
@@ -391,7 +391,7 @@ int partials(RoundCtx* c, const Layout& L, const uint32_t* pts, int R, const lon
     const int ncols_in = nch * (T + 1);
     if (audit == 1) {
       RC_CHECK(hipStreamWaitEvent(c->side, c->ev_main, 0));
-      RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, L.ccols, nch, mask, cs_slot, c->side));
+      RC_CHECK(bsc_sum_rows2(pts, ncols_in, nullptr, R, L.ccols, nch, mask, 0, cs_slot, c->side));
       RC_CHECK(hipEventRecord(c->ev_side, c->side));
     }
     if (L.nwc > 0 && L.ws != nullptr && !defer_wit) {
@@ -416,8 +416,8 @@ int combine(RoundCtx* c, const Layout& L, const unsigned char* recv, int world, 
             double* W_new, long long* h_clock, int audit) {
   const int nch = c->nch, T = c->T;
   if (audit != 0) {
-    RC_CHECK(bsc_sum_rows2((const uint32_t*)recv, (int)(row_bytes / 96), nullptr, world, nullptr, nch, nullptr, c->cs,
-                           c->main));
+    RC_CHECK(bsc_sum_rows2((const uint32_t*)recv, (int)(row_bytes / 96), nullptr, world, nullptr, nch, nullptr, 0,
+                           c->cs, c->main));
     RC_CHECK(hipEventRecord(c->ev_side, c->main));   // bsc_round_audit waits for the sums through ev_side
   }
   RC_CHECK(bsc_recover_w_clock((const long long*)(recv + 96ll * nch), world, row_bytes / 8, nch, T, nullptr, L.ycols,
@@ -582,19 +582,20 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
   RC_CHECK(hipEventRecord(c->ev_pre, c->main));
   RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
   if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
-  RC_CHECK(bsc_softmax_step_ones(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.max_norm,
-                                 t.qs, p.delta, p.qdelta, p.loss, t.lo, ones, c->spec_cap, gs));
+  RC_CHECK(bsc_softmax_step(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.max_norm,
+                            t.qs, p.delta, p.qdelta, p.loss, t.lo, ones, c->spec_cap, gs));
   RC_CHECK(hipEventRecord(p.ev_step, gs));
   RC_CHECK(hipStreamWaitEvent(c->bg, p.ev_step, 0));
   RC_CHECK(bsc_shares_msm(p.qdelta, c->d, t.rows_arange, t.P, c->tbl_pk, t.tbl_wb, c->poly, c->T, c->b0, c->nw, 1,
                           nullptr, nullptr, 0, p.ccom, nullptr, c->bg));
   RC_CHECK(hipEventRecord(p.ev_ccom, c->bg));
-  RC_CHECK(bsc_segment_sum_h(p.ccom, t.P, c->nch, 1, 0, p.jac, p.jac_host, c->bg));
+  RC_CHECK(bsc_segment_sum(p.ccom, t.P, c->nch, 1, 0, p.jac, p.jac_host, c->bg));
   RC_CHECK(hipEventRecord(p.ev_commit, c->bg));
   if (do_gram && t.noise != nullptr) {
     const size_t k = (size_t)(it % 100);   // the noisers' pre-sampled vectors of this iteration
-    RC_CHECK(bsc_gram_stacked(p.delta, t.P, t.noise + k * c->d, t.noise_n, 100ll * c->d, c->d, t.kchunk, p.part, p.gram,
-                              t.counters, t.nn_tab ? t.nn_tab + k * t.noise_n * t.noise_n : nullptr, gs));
+    RC_CHECK(bsc_gram_stacked_range(p.delta, t.P, t.noise + k * c->d, t.noise_n, 100ll * c->d, c->d, t.kchunk, 0, 0,
+                                    p.part, p.gram, t.counters,
+                                    t.nn_tab ? t.nn_tab + k * t.noise_n * t.noise_n : nullptr, gs));
     RC_CHECK(hipEventRecord(p.ev_gram, gs));
   }
   return c->pre_k;
@@ -701,14 +702,15 @@ static int host_wait(hipEvent_t ev, long long timeout_ns = 0) {
   }
 }
 
-// which: 0 = the recovery read-back, 1 = the last audit's read-back, 2 / 3 = audit slot 0 / 1's.  With the round's own communicator, a wait longer
-// than the collective timeout means a rank is gone (the reference's crashed peer): the communicator is aborted
-// -- its kernels return -- and -99 goes back to the engine, which fails the job for the elastic restart
-// (parallel/comm.py), as torch's watchdog does for its own collectives
+// which: 0 = the recovery read-back, 2 / 3 = audit slot 0 / 1's (bsc_round_audit_slot names the slot of the audit
+// queued last; two audits are normally in flight, so the caller keeps the slot it queued).  Any other value: -1,
+// no event touched.  With the round's own communicator, a wait longer than the collective timeout means a rank
+// is gone (the reference's crashed peer): the communicator is aborted -- its kernels return -- and -99 goes back
+// to the engine, which fails the job for the elastic restart (parallel/comm.py), as torch's watchdog does for
+// its own collectives
 extern "C" int bsc_round_wait(void* ctx, int which) {
   RoundCtx* c = (RoundCtx*)ctx;
-  if (c == nullptr) return -1;
-  if (which == 1) which = 2 + c->aud_k;
+  if (c == nullptr || (which != 0 && which != 2 && which != 3)) return -1;
   const hipEvent_t ev = which == 0 ? c->ev_readback : which == 2 ? c->ev_audit : c->ev_audit1;
   const int r = host_wait(ev, c->comm != nullptr ? c->timeout_ns : 0);
   if (r == -99 && c->comm != nullptr && g_rccl.comm_abort != nullptr) {
@@ -917,7 +919,7 @@ extern "C" int bsc_round_agg_multi(void* ctx, const int* node, const int* amap, 
     RC_CHECK(hipStreamWaitEvent(up, c->ev_main, 0));
     if (nspec > 0) RC_CHECK(hipStreamWaitEvent(up, c->ev_side, 0));   // the commitment partials
     RC_CHECK(round_all_gather(c, c->m.send, recv_cs, cs_bytes, up, up));
-    RC_CHECK(bsc_sum_rows2((const uint32_t*)recv_cs, nch, nullptr, world, nullptr, nch, nullptr, c->cs, up));
+    RC_CHECK(bsc_sum_rows2((const uint32_t*)recv_cs, nch, nullptr, world, nullptr, nch, nullptr, 0, c->cs, up));
     RC_CHECK(hipEventRecord(c->ev_side, up));   // bsc_round_audit waits for the totals through ev_side
   }
   if (nspec > 0 && L.nwc > 0) {   // the witness sums (per rank; no consumer in the round)

@@ -842,12 +842,6 @@ extern "C" int bsc_vrf_prove_p(const uint32_t* keys, const int* key_idx, const u
   return (int)hipGetLastError();
 }
 
-extern "C" int bsc_vrf_prove(const uint32_t* keys, const int* key_idx, const uint8_t* alphas, const int* alpha_idx,
-                             int alpha_len, int n, const uint32_t* btab, uint32_t* scratch, uint8_t* pi, uint8_t* beta,
-                             void* stream) {
-  return bsc_vrf_prove_p(keys, key_idx, alphas, alpha_idx, alpha_len, n, btab, scratch, pi, beta, 0, stream);
-}
-
 // ---------------------------------------------------------------- the verifier (the opt-in audit, --vrf-audit)
 // One status per proof, the checks in the order of runtime/vrf.cpp::vrf_verify (the first failing one decides):
 //   0 valid | 1 the public key does not decode | 2 Gamma does not decode | 3 s >= L

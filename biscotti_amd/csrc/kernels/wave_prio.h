@@ -17,7 +17,10 @@
 // The classes apply to one rank per process driving its GPU alone (bsc_wave_prio(1), the default).  With
 // several ranks the engine turns them off (bsc_wave_prio(0)): RCCL's collective kernels run at the default
 // priority and spin on their peers' flags, and under prio-2 share MSMs of two ranks sharing a GPU a collective
-// stalled for 0.1-0.3 s (2-rank RCCL rehearsal).  Each kernel file holds its own flag (one per translation
+// stalled for 0.1-0.3 s (2-rank RCCL rehearsal); one rank per GPU with them on measured slower (docs/PERF.md,
+// round 5), so there is no switch for it.  A kernel's class is fixed in its source; where a kernel argument
+// picks it (commit_only, mask_by_pos, urgent, ahead), the argument tells two uses of one kernel apart and is no
+// tuning switch.  Each kernel file holds its own flag (one per translation
 // unit, named by BSC_PRIO_FLAG before the include) and exports its setter; kernels read it once,
 // wave-uniformly.  The flag has external linkage on purpose: a `static` __device__ variable that the host
 // addresses is externalised with default visibility and read through the GOT (two dependent scalar loads at

@@ -20,10 +20,8 @@ SIGNATURES = {
     "bsc_shares_msm_ka": [P, I, P, I, P, P, I, I, I, I, I, P, I, P, P, P],
     "bsc_alive_compact": [P, I, P, P],
     "bsc_set_alive": [P, P, I, P, P],
-    "bsc_sum_rows": [P, I, P, I, P, I, P, P],
-    "bsc_segment_sum": [P, I, I, I, I, P, P],
-    "bsc_sum_rows2": [P, I, P, I, P, I, P, P, P],
-    "bsc_sum_rows2_pos": [P, I, P, I, P, I, P, P, P],
+    "bsc_segment_sum": [P, I, I, I, I, P, P, P],
+    "bsc_sum_rows2": [P, I, P, I, P, I, P, I, P, P],
     "bsc_round_spec_msm2": [P, I, P, P, P, I, P, I, I, P, P, P, P, P, P],
     "bsc_round_spec_topup": [P, I, P, I, P, I, P, P, I, I, P, P, P, P, P],
     "bsc_round_set_spec_ring": [P, P, I, I],
@@ -36,11 +34,10 @@ SIGNATURES = {
     "bsc_d2h_async": [P, P, L, P],
     "bsc_marshal": [P, I, P, P],
     "bsc_to_affine": [P, I, P, P],
-    "bsc_chunk_check": [P, I, I, P, I, I, P, I, I, P, P],
+    "bsc_chunk_check": [P, I, I, P, I, I, P, I, I, P, P, P],
     "bsc_g1_unmarshal": [P, I, P, P, P, P],
     "bsc_chain_audit": [P, P, P, I, I, P, P, P, I, P, P, I, P, I, I, D, D, D, I, P, P, P, P, P, P, P, P, P],
     # vrf.hip
-    "bsc_vrf_prove": [P, P, P, P, I, I, P, P, P, P, P],
     "bsc_vrf_prove_p": [P, P, P, P, I, I, P, P, P, P, I, P],
     "bsc_vrf_verify": [P, I, P, P, P, I, I, P, P, P, P, P, P, P, P, I, P],
     # schnorr.hip
@@ -53,16 +50,14 @@ SIGNATURES = {
     "bsc_kzg_rows_blocks": [I, I],
     "bsc_kzg_rlc_rows": [P, P, P, P, P, I, I, I, I, P, I, U64, P, P, P],
     # ml.hip
-    "bsc_softmax_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, P, P, P, I, P],
+    "bsc_softmax_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, P, P, P, I, P, I, P],
     "bsc_logreg_step": [P, P, P, P, P, P, I, I, I, U64, P, D, D, P, D, P, P, P],
     "bsc_dp_noise": [P, I, I, P, I, P, U64, I, P, P],
     "bsc_krum": [P, I, I, I, P, P, P, P, I, I, P],
     "bsc_krum_committee": [P, I, I, I, P, I, I, I, I, I, P, I, P, P, P, P, P, P, P, P],
-    "bsc_gram_stacked": [P, I, P, I, L, I, I, P, P, P, P, P],
     "bsc_gram_stacked_range": [P, I, P, I, L, I, I, I, I, P, P, P, P, P],
     "bsc_krum_committee_noise2": [P, I, I, P, P, I, P, I, I, I, I, I, P, I, P, P, P, P, P, P, I, P, P],
     "bsc_krum_committee_noise_ka": [P, I, I, P, P, I, P, I, I, I, I, I, P, I, P, P, P, P, P, P, I, P, P],
-    "bsc_eval_error": [P, P, I, I, I, P, I, I, P, P],
     "bsc_eval_error_rb": [P, P, I, I, I, P, I, I, P, P, P],
     "bsc_eval_error_t_rb": [P, P, I, I, I, I, P, I, P, P, P],
     "bsc_roni_counts_rb": [P, P, L, I, I, P, P, I, P, P, I, I, P, I, I, P, P, P],
@@ -75,7 +70,6 @@ SIGNATURES = {
     "bsc_lsh_codes": [P, P, I, I, P, I, I, P, P],
     "bsc_lsh_count": [P, I, P, I, P, I, D, P, P],
     "bsc_weighted_rows": [P, I, I, P, P, P],
-    "bsc_recover_w": [P, I, I, I, P, P, P, I, P, P, I, I, U64, U64, I, P, D, P, P, P, P, P],
     "bsc_recover_w_clock": [P, I, L, I, I, P, P, P, I, P, P, I, I, U64, U64, I, P, D, P, P, P, P, P, P, P, P],
     "bsc_sum_rows_i64_tail": [P, I, L, P, P, L, P],
     # round.hip
@@ -97,9 +91,7 @@ SIGNATURES = {
     "bsc_round_after_gather": [P, P, I, L, I, P, P, I, I, I, P],
     "bsc_ring_pick": [P, I, P, P, P],
     "bsc_rccl_load": [C.c_char_p],
-    "bsc_set_side_prio": [I],
     "bsc_sum_cols_serial": [P, I, I, P, I, P, P, P],
-    "bsc_set_witness_tree": [I],
     "bsc_rccl_unique_id": [P],
     "bsc_round_comm_init": [P, P, I, I, P, I, D],
     "bsc_round_bind_multi": [P, P, P, L, P, I, P, P, P, I, I, I, P, P, L],

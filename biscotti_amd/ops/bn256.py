@@ -204,17 +204,22 @@ class DeviceCommitEngine:
                                      _ptr(partial), _ptr(out), _stream()), "commit_rows")
         return out
 
-    def check_chunks(self, coeffs: torch.Tensor, csum: torch.Tensor) -> torch.Tensor:
+    def check_chunks(self, coeffs: torch.Tensor, csum: torch.Tensor, h_ok: torch.Tensor | None = None) -> torch.Tensor:
         """Aggregate audit: ok[m, k] = 1 iff the chunk commitment of the recovered coefficients
         coeffs[k] (int64 [nchunks, poly]) equals miner m's summed chunk commitment csum[m, k]
-        (Jacobian int32 [nm, nchunks, 24]) -- verifyCommitment (kyber.go:564-577) on the aggregate."""
+        (Jacobian int32 [nm, nchunks, 24]) -- verifyCommitment (kyber.go:564-577) on the aggregate.
+        h_ok: optional pinned int32 [nm, nchunks] the kernel mirrors ok into (valid once the stream has passed it)."""
         assert coeffs.dtype == torch.int64 and tuple(coeffs.shape) == (self.nchunks, self.poly)
         assert csum.dtype == torch.int32 and csum.dim() == 3 and tuple(csum.shape[1:]) == (self.nchunks, 24)
         coeffs, csum = coeffs.contiguous(), csum.contiguous()
         nm = csum.shape[0]
         ok = torch.empty((nm, self.nchunks), dtype=torch.int32, device=self.device)
+        if h_ok is not None:
+            assert h_ok.dtype == torch.int32 and h_ok.is_pinned() and h_ok.is_contiguous()
+            assert tuple(h_ok.shape) == (nm, self.nchunks)
         _check(hip().bsc_chunk_check(_ptr(coeffs), self.d, self.poly, _ptr(self.tbl_pk), self.b0, self.nw, _ptr(csum),
-                                     nm, self.nchunks, _ptr(ok), _stream()), "chunk_check")
+                                     nm, self.nchunks, _ptr(ok), None if h_ok is None else h_ok.data_ptr(),
+                                     _stream()), "chunk_check")
         return ok
 
     def kzg_rlc(self, csum: torch.Tensor, wsum: torch.Tensor, ys: torch.Tensor, xs: torch.Tensor, spm: int,
@@ -343,7 +348,7 @@ class DeviceCommitEngine:
         """Full-vector commitment per row = sum of its chunk commitments. Returns Jacobian [n, 24]."""
         n, nch, S, _ = pts.shape
         out = torch.empty((n, 24), dtype=torch.int32, device=self.device)
-        _check(hip().bsc_segment_sum(_ptr(pts), n, nch, S, S - 1, _ptr(out), _stream()), "segment_sum")
+        _check(hip().bsc_segment_sum(_ptr(pts), n, nch, S, S - 1, _ptr(out), None, _stream()), "segment_sum")
         return out
 
 
@@ -365,7 +370,7 @@ def sum_rows(pts: torch.Tensor, rows: torch.Tensor | None, cols: torch.Tensor | 
     if row_mask is not None:
         assert row_mask.dtype == torch.int32 and row_mask.numel() == R
     out = torch.empty((ncols, 24), dtype=torch.int32, device=pts.device)
-    _check(hip().bsc_sum_rows2(_ptr(pts), Cn, _ptr(rows), nrows, _ptr(cols), ncols, _ptr(row_mask), _ptr(out),
+    _check(hip().bsc_sum_rows2(_ptr(pts), Cn, _ptr(rows), nrows, _ptr(cols), ncols, _ptr(row_mask), 0, _ptr(out),
                                _stream()), "sum_rows2")
     return out
 

@@ -102,7 +102,7 @@ def softmax_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max
         assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
         _check(hip().bsc_softmax_step(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, d_out, B, P, seed & (2**64 - 1),
                                       iteration, float(max_norm), float(qscale), _p(delta), _p(qdelta), _p(loss),
-                                      int(lo), _stream()), "softmax_step")
+                                      int(lo), None, 0, _stream()), "softmax_step")
         return delta, qdelta, loss
     Wm = W.to(torch.float32)
     Wt, bt = Wm[: d_out * d_in].view(d_out, d_in), Wm[d_out * d_in:]
@@ -936,9 +936,11 @@ def recover_rows(ys, mask, ycols, xs, weights: dict, A_dev, basis_dev, poly: int
         W_new, coeffs, status = recover(agg, xs, poly, d, W, qscale)
         return W_new, coeffs, status, agg
     assert ys.dtype == torch.int64 and ys.is_contiguous() and (mask is None or mask.numel() == R)
-    _check(hip().bsc_recover_w(_p(ys), R, nch, T, _p(mask), _p(ycols), _p(xs), npts, _p(A_dev), _p(basis_dev), poly,
-                               weights["shift"], weights["inv_lo"], weights["inv_hi"], d, _p(W), float(qscale),
-                               _p(W_new), _p(coeffs), _p(status), _p(agg), _stream()), "recover_w")
+    # a dense [R][nch][T] tensor (row stride nch * T), no pinned host mirrors
+    _check(hip().bsc_recover_w_clock(_p(ys), R, nch * T, nch, T, _p(mask), _p(ycols), _p(xs), npts, _p(A_dev),
+                                     _p(basis_dev), poly, weights["shift"], weights["inv_lo"], weights["inv_hi"], d,
+                                     _p(W), float(qscale), _p(W_new), _p(coeffs), _p(status), _p(agg), None, None, None,
+                                     _stream()), "recover_w")
     return W_new, coeffs, status, agg
 
 

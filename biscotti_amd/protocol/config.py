@@ -110,25 +110,13 @@ class RunConfig:
     #   spec_all_candidates GPU: the speculative share MSM covers every candidate (every approved worker's
     #                      shares, as each reference worker computes its own), not only the leader's first
     #                      arrivals up to the adaptive horizon (head.py SPEC_MARGIN): the chain must not change
-    #   short_spin         GPU: host waits spin 200 us before polling with sleeps also with one rank (the
-    #                      multi-rank setting; one rank spins up to 5 ms: a sleeping thread wakes late)
-    #   noise_gram_each_round GPU: the noise-aware Gram computes its noise x noise tiles every round instead of
-    #                      copying them from the setup table of the 100 periodic noise Grams (ml.NoiseRows.gram_table)
     #   no_early_front     GPU: the next round's noiser lottery + Krum launch run at its own start instead of at
     #                      the end of the previous round (engine._round_front): the chain must not change
     #   spec_tight         GPU: the speculative MSM's horizon is the leader's cap exactly (no margin, no slack): a
     #                      block reaching past its first cap arrivals is a speculative miss, topped up by the host
     #                      path (tests and measurements of that path): the chain must not change
-    #   wave_prio_multi    GPU: the round kernels' wave priority classes (kernels/wave_prio.h) also with several
-    #                      ranks (default: one rank only; the collectives' kernels run at the default class)
     #   multi_early_front  GPU, several ranks with the native collectives: the next round's front at the end of the
     #                      previous round as with one rank (engine._early_front_ok; measured slower there)
-    #   side_prio_low      GPU: the full-commitment sums (k_segment_sum) and the aggregate audit (k_chunk_check) one
-    #                      wave-priority class below the speculative share MSM instead of at the critical class
-    #   witness_sums_tree  GPU: the miners' witness sums in k_sum_rows2's LDS-tree form (16 lanes a column) instead of
-    #                      one lane a column (k_sum_cols_serial: ~30 % fewer Jacobian additions)
-    #   side_all_cus       GPU: the speculative share MSM's stream on every CU (default: 3/4 of them, the rest kept for
-    #                      the critical path)
     #   no_spec_front      GPU, one rank: the next round's front at the commit of the block (after the audit wait and
     #                      the read-back) instead of right after the block's build (engine._spec_front_launch): the
     #                      chain must not change
@@ -140,11 +128,8 @@ class RunConfig:
     churn_round_s: ClassVar[float] = 25.44
     MINER_THRESHOLDS: ClassVar[dict] = {"half_samples": 0, "eighth": 8, "tenth": 10}   # -> miner_block_div
     ABLATIONS: ClassVar[tuple] = ("noise_independent", "shared_inbox", "no_miner_cap", "no_roles_proof", "no_pipeline",
-                                  "spec_head_shared", "spec_all_candidates", "short_spin",
-                                  "noise_gram_each_round", "spec_tight", "no_early_front",
-                                  "wave_prio_multi", "multi_early_front", "side_prio_low",
-                                  "witness_sums_tree", "side_all_cus", "no_spec_front",
-                                  "multi_spec_front")
+                                  "spec_head_shared", "spec_all_candidates", "spec_tight", "no_early_front",
+                                  "multi_early_front", "no_spec_front", "multi_spec_front")
 
     def has(self, ablation: str) -> bool:
         """True when `ablation` (one of ABLATIONS) is switched on."""

@@ -156,12 +156,10 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         if self.gpu:
             # wave priority classes (kernels/wave_prio.h): one rank drives its GPU alone; with several ranks the
             # collectives' kernels must not queue behind prio-2 share MSMs
-            B.set_wave_priorities(self.comm.world == 1 or cfg.has("wave_prio_multi"))
-            B.hip().bsc_set_side_prio(1 if cfg.has("side_prio_low") else 0)
-            B.hip().bsc_set_witness_tree(1 if cfg.has("witness_sums_tree") else 0)
+            B.set_wave_priorities(self.comm.world == 1)
             # host waits spin up to 5 ms before sleeping when this rank has its GPU (and a core of the quota) to
             # itself -- one rank, or one rank per GPU; ranks sharing a GPU (rehearsals) spin 200 us
-            S.set_spin(5e-3 if not self._shared_device and not cfg.has("short_spin") else 2e-4)
+            S.set_spin(5e-3 if not self._shared_device else 2e-4)
             self._native = B.NativeSecAgg(self.crypto.eng, self.main_stream, self.side_stream, self.bg_stream,
                                           10.0 ** cfg.precision, witness=self.witness_stream)
             if self.comm.world > 1:
@@ -258,10 +256,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         VRF outputs / Krum, and the critical path keeps the rest)."""
         lo, hi = torch.cuda.Stream.priority_range()
         self.main_stream = torch.cuda.Stream(device=self.dev, priority=hi)
-        # (side_all_cus: on every CU -- emulated rank 0 of 2 measured 0.959 vs 0.991 ms on one box and no different on
-        # another, docs/PERF.md round 6: the quarter stays with the critical path)
-        full = self.cfg.has("side_all_cus")
-        self.side_stream, self.side_cus = B.cu_masked_stream(self.dev, 0 if full else SIDE_STREAM_SKIP_EVERY)
+        # (on every CU it measured no different, docs/PERF.md round 6: the quarter stays with the critical path)
+        self.side_stream, self.side_cus = B.cu_masked_stream(self.dev, SIDE_STREAM_SKIP_EVERY)
         # work the round's end waits for at most (the pre-step's commitments: the block carries them)
         self.bg_stream = torch.cuda.Stream(device=self.dev, priority=lo)
         # work no consumer in the round waits for (the miners' witness sums): on bg they queued the

@@ -258,10 +258,8 @@ class RoundHeadMixin:
 
     def _noise_gram_table(self):
         """GPU: the [100, N, N] Gram of each iteration's noise rows (NoiseRows.gram_table, built at setup), whose
-        tiles the noise-aware Gram copies instead of computing; None on the CPU or with the
-        noise_gram_each_round ablation."""
-        if not (self.gpu and self.noise_rows is not None and self.noise_rows.table is not None) or \
-                self.cfg.has("noise_gram_each_round"):
+        tiles the noise-aware Gram copies instead of computing; None on the CPU, where the Gram computes them."""
+        if not (self.gpu and self.noise_rows is not None and self.noise_rows.table is not None):
             return None
         return self.noise_rows.gram_table()
 

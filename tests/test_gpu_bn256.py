@@ -114,7 +114,7 @@ def test_shares_msm_matches_host(rt, d, secret, scale, b0):
 
 
 def test_sum_rows2_pos_mask_and_early_commitment_sums(rt):
-    """bsc_sum_rows2_pos (mask indexed by the position in the row list): the audit's early commitment sums
+    """bsc_sum_rows2 with mask_by_pos (mask indexed by the position in the row list): the audit's early commitment sums
     over the pre-step's per-peer chunk commitments equal the sums over the share MSM's commitment slots."""
     from biscotti_amd.native import hip
     from biscotti_amd.ops import bn256 as B
@@ -127,8 +127,8 @@ def test_sum_rows2_pos_mask_and_early_commitment_sums(rt):
     rows = torch.tensor([4, 1, 5, 0], dtype=torch.int32, device="cuda")          # speculative row -> peer row
     mask = torch.tensor([1, 0, 1, 1], dtype=torch.int32, device="cuda")          # alive flags by position
     out = torch.empty((eng.nchunks, 24), dtype=torch.int32, device="cuda")
-    assert hip().bsc_sum_rows2_pos(ccom.data_ptr(), eng.nchunks, rows.data_ptr(), 4, None, eng.nchunks,
-                                   mask.data_ptr(), out.data_ptr(), None) == 0
+    assert hip().bsc_sum_rows2(ccom.data_ptr(), eng.nchunks, rows.data_ptr(), 4, None, eng.nchunks,
+                               mask.data_ptr(), 1, out.data_ptr(), None) == 0
     pts, _ = eng.shares(coeffs, rows)                                            # commitment slots = column T
     ref = B.sum_rows(pts.reshape(4, -1, 24), None, torch.arange(eng.nchunks, dtype=torch.int32, device="cuda") * 22 + 21,
                      row_mask=mask)
@@ -191,7 +191,13 @@ def test_chunk_check_audits_aggregate(rt, d, b0):
     bad = csum.clone()
     bad[0, 1] = csum[0, 2]                   # miner 1 reports a wrong chunk-1 sum
     both = torch.cat([csum, bad])
-    ok = eng.check_chunks(torch.from_numpy(coeffs).cuda(), both).cpu().numpy()
+    # the smallest d also takes the pinned host mirror, which the kernel writes beside ok
+    h_ok = torch.full((2, eng.nchunks), -1, dtype=torch.int32).pin_memory() if d == 57 else None
+    ok = eng.check_chunks(torch.from_numpy(coeffs).cuda(), both, h_ok)
+    if h_ok is not None:
+        torch.cuda.current_stream().synchronize()
+        np.testing.assert_array_equal(h_ok.numpy(), ok.cpu().numpy())
+    ok = ok.cpu().numpy()
     assert ok[0].all()
     assert ok[1, 1] == 0 and ok[1].sum() == eng.nchunks - 1
     wrong = coeffs.copy()
@@ -248,7 +254,7 @@ def test_sum_cols_serial_masked_witness_sums(rt):
                                          got.data_ptr(), None) == 0
         ref = torch.empty_like(got)
         assert hip().bsc_sum_rows2(flat.data_ptr(), ncols_in, None, 5, cols.data_ptr(), cols.numel(), mask.data_ptr(),
-                                   ref.data_ptr(), None) == 0
+                                   0, ref.data_ptr(), None) == 0
         np.testing.assert_array_equal(B.marshal(got).cpu().numpy(), B.marshal(ref).cpu().numpy())
         kept = [i for i, m in enumerate(mask_l) if m]
         if kept:

@@ -560,6 +560,18 @@ def test_partials_gather_recovery_swapped_commitment(two_ctx, shares7):
     _assert_same_as_one_rank(got, one)
 
 
+def test_round_wait_takes_a_slot(two_ctx):
+    """bsc_round_wait names what it waits for: 0 the recovery's read-back, 2 / 3 an audit slot.  Anything else --
+    the former 1 ("the audit queued last") included -- is refused before an event is touched; nothing is queued or
+    launched here."""
+    torch.cuda.synchronize()
+    for c in (two_ctx.multi, two_ctx.single):
+        for which in (1, 4, -1):
+            assert hip().bsc_round_wait(c.na.ctx, which) == -1
+        assert hip().bsc_round_wait(c.na.ctx, 0) == 0
+    assert hip().bsc_round_wait(None, 0) == -1
+
+
 def test_emulated_collectives(eng, shares7):
     """Rank 0 of 4 alone (every collective one replicate launch): bsc_round_agg_multi leaves rank 0's send pieces in
     every slot of the two-piece receive layout ([world][cs] then [world][ys | clock]), recovers 4 times rank 0's

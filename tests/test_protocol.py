@@ -311,6 +311,12 @@ def test_cli_defaults_match_runconfig():
 
     with pytest.raises(ValueError):
         RunConfig(ablation="early_krum").validate()
+    # measured and not adopted (docs/PERF.md): removed with their code paths, no alias kept
+    for name in ("wave_prio_multi", "side_prio_low", "witness_sums_tree", "side_all_cus", "short_spin",
+                 "noise_gram_each_round"):
+        with pytest.raises(ValueError):
+            RunConfig(ablation=name).validate()
+    assert len(RunConfig.ABLATIONS) <= 12
 
 
 def test_route_view_matches_route_shares_and_leader_view():

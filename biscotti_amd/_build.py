@@ -118,7 +118,7 @@ def build_selftest(sanitize: bool | str = True) -> Path:
     out.parent.mkdir(parents=True, exist_ok=True)
     srcs = [s for s in sorted(rt_dir.glob("*.cpp")) if s.name != "bindings.cpp"]
     srcs.append(CSRC / "selftest" / "selftest.cpp")
-    flags = ["-O1", "-g", "-std=c++17", "-pthread", f"-I{rt_dir}", "-fno-omit-frame-pointer"]
+    flags = ["-O1", "-g", "-std=c++17", "-pthread", f"-I{rt_dir}", f"-I{CSRC / 'kernels'}", "-fno-omit-frame-pointer"]
     if mode == "asan":
         flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
     elif mode == "tsan":

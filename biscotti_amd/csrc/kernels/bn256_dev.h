@@ -153,9 +153,9 @@ __device__ __forceinline__ jac jac_inf() {
 __device__ __forceinline__ bool jac_is_inf(const jac& p) { return fp_is_zero(p.z); }
 __device__ __forceinline__ bool aff_is_inf(const aff& q) { return fp_is_zero(q.y); }
 
-// dbl-2009-l
-__device__ inline jac jac_dbl(const jac& p) {
-  if (jac_is_inf(p)) return p;
+// dbl-2009-l, without the infinity test: infinity (z = 0) stays infinity, z' = 2 y z = 0.  Force-inlined
+// for the chains that double every step (kzg.hip): as a call, its frame would live in scratch.
+__device__ __forceinline__ jac jac_dbl_nocheck(const jac& p) {
   fp A = fp_sqr(p.x);
   fp B = fp_sqr(p.y);
   fp C = fp_sqr(B);
@@ -170,6 +170,11 @@ __device__ inline jac jac_dbl(const jac& p) {
   r.y = fp_sub(fp_mul(E, fp_sub(D, r.x)), c8);
   r.z = fp_dbl(fp_mul(p.y, p.z));
   return r;
+}
+
+__device__ inline jac jac_dbl(const jac& p) {
+  if (jac_is_inf(p)) return p;
+  return jac_dbl_nocheck(p);
 }
 
 // add-2007-bl, complete for the special cases (P==Q, P==-Q, infinities)
@@ -306,6 +311,19 @@ __device__ __forceinline__ aff ld_aff(const uint32_t* p) {
 __device__ __forceinline__ void st_aff(uint32_t* p, const aff& a) {
   st_fp(p, a.x);
   st_fp(p + 8, a.y);
+}
+
+// Block-level LDS tree: every lane t has stored its Jacobian partial sum at sh + 24 t (infinity where it has
+// none) and the block has passed a barrier since; the first n lanes (n <= lanes of the block) hold the terms.
+// Afterwards sh[0..23] is their sum.  Only the smallest power of two >= n lanes take part (n is often a
+// handful: 3 levels, not 8).  Every lane of the block must call it.
+__device__ __forceinline__ void lds_tree_sum(uint32_t* sh, int t, int n) {
+  int top = 1;
+  while (top < n) top <<= 1;
+  for (int s = top >> 1; s > 0; s >>= 1) {
+    if (t < s) st_jac(sh + t * 24, jac_add(ld_jac(sh + t * 24), ld_jac(sh + (t + s) * 24)));
+    __syncthreads();
+  }
 }
 
 }  // namespace bn

@@ -36,73 +36,98 @@ __device__ __forceinline__ unsigned long long kzg_r(unsigned long long seed, uns
   return (z ^ (z >> 31)) | 1ull;
 }
 
-// dbl-2009-l, force-inlined here (bn::jac_dbl is a call: its frame would live in scratch)
-__device__ __forceinline__ jac kz_dbl(const jac& p) {
-  fp A = fp_sqr(p.x);
-  fp B = fp_sqr(p.y);
-  fp C = fp_sqr(B);
-  fp t = fp_sqr(fp_add(p.x, B));
-  t = fp_sub(fp_sub(t, A), C);
-  fp D = fp_dbl(t);
-  fp E = fp_add(fp_dbl(A), A);
-  fp F = fp_sqr(E);
-  jac r;
-  r.x = fp_sub(F, fp_dbl(D));
-  fp c8 = fp_dbl(fp_dbl(fp_dbl(C)));
-  r.y = fp_sub(fp_mul(E, fp_sub(D, r.x)), c8);
-  r.z = fp_dbl(fp_mul(p.y, p.z));
-  return r;   // infinity (z = 0) stays infinity: z' = 2 y z = 0
+// 192-bit scalars: three named limbs, shifted in registers (an indexed limb array would be a run-time-indexed
+// private array: scratch, see the header).  Two's complement where a sign is meant.
+struct u192 {
+  unsigned long long w0, w1, w2;
+};
+
+__device__ __forceinline__ void u192_neg(u192& z) {
+  z.w0 = ~z.w0; z.w1 = ~z.w1; z.w2 = ~z.w2;
+  z.w0 += 1;
+  const unsigned long long c0 = z.w0 == 0;
+  z.w1 += c0;
+  z.w2 += (c0 && z.w1 == 0);
 }
 
-// k * P for a 192-bit unsigned k = (k2:k1:k0), left to right over its bit length
-__device__ __forceinline__ jac jac_mul_192(const jac& p, unsigned long long k0, unsigned long long k1, unsigned long long k2) {
-  int nbits;
-  if (k2) nbits = 192 - __clzll(k2);
-  else if (k1) nbits = 128 - __clzll(k1);
-  else if (k0) nbits = 64 - __clzll(k0);
-  else return jac_inf();
-  // left-align the top bit at position 191
-  int sh = 192 - nbits;
-  while (sh >= 64) { k2 = k1; k1 = k0; k0 = 0; sh -= 64; }
+// z += r * y (signed y, every int64 included), modulo 2^192
+__device__ __forceinline__ void u192_add_signed_product(u192& z, unsigned long long r, long long y) {
+  const unsigned long long m = y < 0 ? 0ull - (unsigned long long)y : (unsigned long long)y;
+  u192 p = {r * m, __umul64hi(r, m), 0};
+  if (y < 0) u192_neg(p);
+  z.w0 += p.w0;
+  const unsigned long long c0 = z.w0 < p.w0;
+  const unsigned long long t1 = z.w1 + p.w1;
+  const unsigned long long c1 = t1 < z.w1;
+  z.w1 = t1 + c0;
+  const unsigned long long c1b = z.w1 < c0;
+  z.w2 += p.w2 + c1 + c1b;
+}
+
+// z = |z|; returns whether z was negative
+__device__ __forceinline__ bool u192_abs(u192& z) {
+  const bool neg = z.w2 >> 63;
+  if (neg) u192_neg(z);
+  return neg;
+}
+
+__device__ __forceinline__ int u192_bits(const u192& k) {
+  if (k.w2) return 192 - __clzll(k.w2);
+  if (k.w1) return 128 - __clzll(k.w1);
+  if (k.w0) return 64 - __clzll(k.w0);
+  return 0;
+}
+
+__device__ __forceinline__ void u192_shl(u192& k, int sh) {
+  while (sh >= 64) { k.w2 = k.w1; k.w1 = k.w0; k.w0 = 0; sh -= 64; }
   if (sh) {
-    k2 = (k2 << sh) | (k1 >> (64 - sh));
-    k1 = (k1 << sh) | (k0 >> (64 - sh));
-    k0 <<= sh;
+    k.w2 = (k.w2 << sh) | (k.w1 >> (64 - sh));
+    k.w1 = (k.w1 << sh) | (k.w0 >> (64 - sh));
+    k.w0 <<= sh;
   }
+}
+
+// the step of a left-to-right chain: returns bit 191 and shifts left by one
+__device__ __forceinline__ bool u192_shl1_top(u192& k) {
+  const bool top = k.w2 >> 63;
+  k.w2 = (k.w2 << 1) | (k.w1 >> 63); k.w1 = (k.w1 << 1) | (k.w0 >> 63); k.w0 <<= 1;
+  return top;
+}
+
+// Left-aligns k (top bit at position 191) and takes that bit off; returns k's bit length, 0 for k = 0.
+// A chain then starts from the base and runs bits - 1 steps.
+__device__ __forceinline__ int u192_chain_start(u192& k) {
+  const int nbits = u192_bits(k);
+  if (nbits == 0) return 0;
+  u192_shl(k, 192 - nbits);
+  u192_shl1_top(k);
+  return nbits;
+}
+
+// k * P for a 192-bit unsigned k, left to right over its bit length
+__device__ __forceinline__ jac jac_mul_192(const jac& p, u192 k) {
+  const int nbits = u192_chain_start(k);
+  if (nbits == 0) return jac_inf();
   jac acc = p;   // the top bit
-  k2 = (k2 << 1) | (k1 >> 63); k1 = (k1 << 1) | (k0 >> 63); k0 <<= 1;
   for (int b = 1; b < nbits; ++b) {
-    acc = kz_dbl(acc);
-    if (k2 >> 63) acc = jac_add(acc, p);
-    k2 = (k2 << 1) | (k1 >> 63); k1 = (k1 << 1) | (k0 >> 63); k0 <<= 1;
+    acc = jac_dbl_nocheck(acc);
+    if (u192_shl1_top(k)) acc = jac_add(acc, p);
   }
   return acc;
 }
 
 // same with an affine base (mixed additions: 11 products instead of 16)
-__device__ __forceinline__ jac aff_mul_192(const aff& q, unsigned long long k0, unsigned long long k1, unsigned long long k2) {
+__device__ __forceinline__ jac aff_mul_192(const aff& q, u192 k) {
   if (aff_is_inf(q)) return jac_inf();
-  int nbits;
-  if (k2) nbits = 192 - __clzll(k2);
-  else if (k1) nbits = 128 - __clzll(k1);
-  else if (k0) nbits = 64 - __clzll(k0);
-  else return jac_inf();
-  int sh = 192 - nbits;
-  while (sh >= 64) { k2 = k1; k1 = k0; k0 = 0; sh -= 64; }
-  if (sh) {
-    k2 = (k2 << sh) | (k1 >> (64 - sh));
-    k1 = (k1 << sh) | (k0 >> (64 - sh));
-    k0 <<= sh;
-  }
+  const int nbits = u192_chain_start(k);
+  if (nbits == 0) return jac_inf();
   jac acc;
   acc.x = q.x;
   acc.y = q.y;
   acc.z = fp_one();
-  k2 = (k2 << 1) | (k1 >> 63); k1 = (k1 << 1) | (k0 >> 63); k0 <<= 1;
   for (int b = 1; b < nbits; ++b) {
-    acc = kz_dbl(acc);
-    if (k2 >> 63) acc = jac_add_aff(acc, q);
-    k2 = (k2 << 1) | (k1 >> 63); k1 = (k1 << 1) | (k0 >> 63); k0 <<= 1;
+    acc = jac_dbl_nocheck(acc);
+    if (u192_shl1_top(k)) acc = jac_add_aff(acc, q);
   }
   return acc;
 }
@@ -139,54 +164,28 @@ extern "C" __global__ void __launch_bounds__(KZ_THREADS) k_kzg_rlc(
     const unsigned long long r = kzg_r(seed, (unsigned long long)g);
     const long long row = (long long)(j / spm) * nch * spm + (long long)k * spm + j % spm;
     const jac w = ld_jac(wsum + row * 24);
-    a = jac_mul_192(w, r, 0, 0);
+    a = jac_mul_192(w, u192{r, 0, 0});
     const int x = xs[(long long)(k / nch_round) * npts + j];
     const unsigned ax = x < 0 ? unsigned(-x) : unsigned(x);
-    l2 = jac_mul_192(a, ax, 0, 0);
+    l2 = jac_mul_192(a, u192{ax, 0, 0});
     if (x < 0) l2 = jac_neg(l2);
   } else if (g < nw + nch) {
     const int k = (int)(g - nw);
-    unsigned long long lo = 0, hi = 0;
+    u192 R = {0, 0, 0};   // R = sum_j r_kj: 128 bits
     for (int j = 0; j < npts; ++j) {
       const unsigned long long r = kzg_r(seed, (unsigned long long)k * npts + j);
-      lo += r;
-      hi += lo < r;
+      R.w0 += r;
+      R.w1 += R.w0 < r;
     }
-    l1 = jac_mul_192(ld_jac(csum + (long long)k * 24), lo, hi, 0);
+    l1 = jac_mul_192(ld_jac(csum + (long long)k * 24), R);
   } else if (g < nw + 2 * nch) {
     const int k = (int)(g - nw - nch);
-    // Z = sum_j r_kj * y_kj, two's complement over 192 bits
-    unsigned long long z0 = 0, z1 = 0, z2 = 0;
-    for (int j = 0; j < npts; ++j) {
-      const unsigned long long r = kzg_r(seed, (unsigned long long)k * npts + j);
-      const long long y = ys[(long long)k * npts + j];
-      const unsigned long long m = y < 0 ? 0ull - (unsigned long long)y : (unsigned long long)y;
-      unsigned long long p0 = r * m, p1 = __umul64hi(r, m), p2 = 0;
-      if (y < 0) {   // negate the 192-bit product
-        p0 = ~p0; p1 = ~p1; p2 = ~0ull;
-        p0 += 1;
-        const unsigned long long c0 = p0 == 0;
-        p1 += c0;
-        p2 += (c0 && p1 == 0);
-      }
-      z0 += p0;
-      const unsigned long long c0 = z0 < p0;
-      const unsigned long long t1 = z1 + p1;
-      const unsigned long long c1 = t1 < z1;
-      z1 = t1 + c0;
-      const unsigned long long c1b = z1 < c0;
-      z2 += p2 + c1 + c1b;
-    }
-    const bool neg = z2 >> 63;
-    if (neg) {
-      z0 = ~z0; z1 = ~z1; z2 = ~z2;
-      z0 += 1;
-      const unsigned long long c0 = z0 == 0;
-      z1 += c0;
-      z2 += (c0 && z1 == 0);
-    }
+    u192 Z = {0, 0, 0};   // Z = sum_j r_kj * y_kj
+    for (int j = 0; j < npts; ++j)
+      u192_add_signed_product(Z, kzg_r(seed, (unsigned long long)k * npts + j), ys[(long long)k * npts + j]);
+    const bool neg = u192_abs(Z);
     const aff b = ld_aff(bases + (long long)(k % nch_round) * base_stride * 16);
-    l1 = aff_mul_192(b, z0, z1, z2);
+    l1 = aff_mul_192(b, Z);
     if (!neg) l1 = jac_neg(l1);   // the term is -Z_k B_k
   }
   l1 = block_sum(l1, lds);
@@ -256,22 +255,6 @@ namespace {
 
 constexpr int KR_M = 4;   // chunks per lane: 8 + 16 KR_M products per bit instead of 24 KR_M
 
-__device__ __forceinline__ void shl192(unsigned long long& k0, unsigned long long& k1, unsigned long long& k2, int sh) {
-  while (sh >= 64) { k2 = k1; k1 = k0; k0 = 0; sh -= 64; }
-  if (sh) {
-    k2 = (k2 << sh) | (k1 >> (64 - sh));
-    k1 = (k1 << sh) | (k0 >> (64 - sh));
-    k0 <<= sh;
-  }
-}
-
-__device__ __forceinline__ int bits192(unsigned long long k0, unsigned long long k1, unsigned long long k2) {
-  if (k2) return 192 - __clzll(k2);
-  if (k1) return 128 - __clzll(k1);
-  if (k0) return 64 - __clzll(k0);
-  return 0;
-}
-
 }  // namespace
 
 // grid (nslab + nl1, n).  Blocks x < nslab: witness terms of chunks [x * slab, +slab) -> partial (A, L2);
@@ -297,7 +280,7 @@ extern "C" __global__ void __launch_bounds__(KZ_THREADS) k_kzg_rows(
       const int k0 = bx * G * KR_M + g;
       const uint32_t* w0 = prow + (long long)c * 24;
       for (int b = 63; b >= 0; --b) {
-        u = kz_dbl(u);
+        u = jac_dbl_nocheck(u);
 #pragma unroll 1
         for (int m = 0; m < KR_M; ++m) {
           const int k = k0 + m * G;
@@ -309,60 +292,35 @@ extern "C" __global__ void __launch_bounds__(KZ_THREADS) k_kzg_rows(
       }
       const int x = xs[j];
       const unsigned ax = x < 0 ? unsigned(-x) : unsigned(x);
-      v = jac_mul_192(u, ax, 0, 0);
+      v = jac_mul_192(u, u192{ax, 0, 0});
       if (x < 0) v = jac_neg(v);
     }
   } else {
     const int k = (bx - nslab) * KZ_THREADS + t;
     if (k < nch) {
       // R = sum_j r (128-bit), Z = sum_j r * y (two's complement over 192 bits)
-      unsigned long long r0 = 0, r1 = 0, r2 = 0, z0 = 0, z1 = 0, z2 = 0;
+      u192 R = {0, 0, 0}, Z = {0, 0, 0};
       for (int j = 0; j < npts; ++j) {
         const int c = cols[j];
         if ((unsigned)c >= (unsigned)T) continue;
         const unsigned long long r = kzg_r(s, (unsigned long long)k * npts + j);
-        r0 += r;
-        r1 += r0 < r;
-        const long long y = yrow[(long long)k * T + c];
-        const unsigned long long m = y < 0 ? 0ull - (unsigned long long)y : (unsigned long long)y;
-        unsigned long long p0 = r * m, p1 = __umul64hi(r, m), p2 = 0;
-        if (y < 0) {   // negate the 192-bit product
-          p0 = ~p0; p1 = ~p1; p2 = ~0ull;
-          p0 += 1;
-          const unsigned long long c0 = p0 == 0;
-          p1 += c0;
-          p2 += (c0 && p1 == 0);
-        }
-        z0 += p0;
-        const unsigned long long c0 = z0 < p0;
-        const unsigned long long t1 = z1 + p1;
-        const unsigned long long c1 = t1 < z1;
-        z1 = t1 + c0;
-        const unsigned long long c1b = z1 < c0;
-        z2 += p2 + c1 + c1b;
+        R.w0 += r;
+        R.w1 += R.w0 < r;
+        u192_add_signed_product(Z, r, yrow[(long long)k * T + c]);
       }
-      const bool neg = z2 >> 63;
-      if (neg) {
-        z0 = ~z0; z1 = ~z1; z2 = ~z2;
-        z0 += 1;
-        const unsigned long long c0 = z0 == 0;
-        z1 += c0;
-        z2 += (c0 && z1 == 0);
-      }
+      const bool neg = u192_abs(Z);
       const jac C = ld_jac(prow + (long long)k * cstride + (long long)T * 24);
       aff B = ld_aff(bases + (long long)k * base_stride * 16);
       if (!neg) B = aff_neg(B);   // the term is -Z B
       // R C + |Z| (+-B): one chain over the longer scalar, both left-aligned at bit 191
-      const int nr = bits192(r0, r1, r2), nz = bits192(z0, z1, z2);
+      const int nr = u192_bits(R), nz = u192_bits(Z);
       const int nbits = nr > nz ? nr : nz;
-      shl192(r0, r1, r2, 192 - nbits);
-      shl192(z0, z1, z2, 192 - nbits);
+      u192_shl(R, 192 - nbits);
+      u192_shl(Z, 192 - nbits);
       for (int b = 0; b < nbits; ++b) {
-        u = kz_dbl(u);
-        if (r2 >> 63) u = jac_add(u, C);
-        if (z2 >> 63) u = jac_add_aff(u, B);
-        r2 = (r2 << 1) | (r1 >> 63); r1 = (r1 << 1) | (r0 >> 63); r0 <<= 1;
-        z2 = (z2 << 1) | (z1 >> 63); z1 = (z1 << 1) | (z0 >> 63); z0 <<= 1;
+        u = jac_dbl_nocheck(u);
+        if (u192_shl1_top(R)) u = jac_add(u, C);
+        if (u192_shl1_top(Z)) u = jac_add_aff(u, B);
       }
     }
   }

@@ -23,47 +23,14 @@
 #include <vector>
 
 #include "bn256_dev.h"
+#include "fixed_base.h"   // the tables' window plan: geometry, digit walk, argument checks
 #include "launchers.h"
+#include "msm_lanes.h"    // the share MSM's lane map, xcd_remap
 #define BSC_PRIO_FLAG bsc_prio_on_msm
 #include "wave_prio.h"
 BSC_PRIO_SETTER(bsc_wave_prio_msm)
 
 using namespace bn;
-
-namespace {
-
-constexpr int TBL_ENTRIES = 128;  // entries of an 8-bit signed window
-
-// Window plan of every fixed-base table: window 0 is B0 bits wide (2^(B0-1) entries: signed digits
-// |d| <= 2^(B0-1)), windows 1..NW-1 are 8 bits (128 entries).  Per base the entries are laid out
-// window 0 first, then 128 per further window; entry (w, |d|) of a base is entry index
-//   w == 0 ? |d| - 1 : E0 + (w - 1) * 128 + |d| - 1,   E0 = 2^(B0-1).
-// A wide first window turns the typical quantised update coefficient (|q| < 2^13) into ONE mixed
-// addition instead of two: HBM is spent (tens of GB of tables) to halve the MSM arithmetic.
-__device__ __forceinline__ int win_bits(int w, int B0) { return w ? 8 : B0; }
-__device__ __forceinline__ int win_entry(int w, int ad, int E0) { return (w ? E0 + (w - 1) * TBL_ENTRIES : 0) + ad - 1; }
-// next signed digit of width `bits` from (m, carry); digits lie in (-2^(bits-1), 2^(bits-1)]
-__device__ __forceinline__ int recode(unsigned long long& m, int& carry, int bits) {
-  int dg = (int)(m & ((1ull << bits) - 1)) + carry;
-  m >>= bits;
-  if (dg > (1 << (bits - 1))) {
-    dg -= 1 << bits;
-    carry = 1;
-  } else {
-    carry = 0;
-  }
-  return dg;
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
-  // bijective: blocks that share an XCD (bid % 8) get a contiguous logical range
-  const int q = nblocks / 8, r = nblocks % 8;
-  const int xcd = bid % 8, idx = bid / 8;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + idx;
-}
-
-}  // namespace
 
 // ------------------------------------------------------------------ test kernels
 extern "C" __global__ void __launch_bounds__(256) k_fp_mul(const uint32_t* a, const uint32_t* b, uint32_t* out, int n, int op) {
@@ -129,25 +96,25 @@ extern "C" __global__ void __launch_bounds__(128) k_witness_bases(const uint32_t
 
 // ------------------------------------------------------------------ fixed-base tables
 // Thread per (base b, run): a run is 128 consecutive entries of one window -- window 0 has
-// E0/128 runs, every 8-bit window one.  Run r of window w holds (128 r + k) * 2^shift_w * base,
-// k = 1..128, shift_0 = 0, shift_w = B0 + 8 (w - 1).  Base index b = outer * inner + in; entry e
+// E0/128 runs, every 8-bit window one (fixed_base.h).  Run r of window w holds (128 r + k) * 2^shift_w * base,
+// k = 1..128.  Base index b = outer * inner + in; entry e
 // of base b is stored at table + 16 * (outer * s_outer + e * s_e + in * s_in).
 // scratch: per thread 128 x 32 u32 (Jacobian + exclusive prefix product of the Z's).
 extern "C" __global__ void __launch_bounds__(64) k_fb_table(const uint32_t* bases, int bases_are_jac, int b0, int nb,
                                                            int inner, int B0, int NW, long long s_outer,
                                                            long long s_e, long long s_in, uint32_t* table,
                                                            uint32_t* scratch) {
-  const int E0 = 1 << (B0 - 1);
-  const int R0 = E0 / TBL_ENTRIES;
-  const int runs = R0 + NW - 1;
+  const FbPlan plan = fb_plan(B0, NW);
+  const int R0 = plan.E0 / FB_ENTRIES;   // runs of window 0
+  const int runs = fb_runs(plan);
   const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (long long)nb * runs) return;
   const int bl = (int)(g / runs), run = (int)(g % runs);
   const int b = b0 + bl;
   const int w = run < R0 ? 0 : run - R0 + 1;
   const int r = run < R0 ? run : 0;
-  const int shift = w ? B0 + 8 * (w - 1) : 0;
-  const int e0 = w ? E0 + (w - 1) * TBL_ENTRIES : r * TBL_ENTRIES;
+  const int shift = fb_window_shift(plan, w);
+  const int e0 = fb_entry(plan, w, 1) + r * FB_ENTRIES;   // the run's first entry
   jac P;
   if (bases_are_jac) {
     P = ld_jac(bases + 24 * (size_t)b);
@@ -156,10 +123,10 @@ extern "C" __global__ void __launch_bounds__(64) k_fb_table(const uint32_t* base
     P = jac_add_aff(jac_inf(), a);
   }
   for (int i = 0; i < shift; ++i) P = jac_dbl(P);
-  uint32_t* sc = scratch + (size_t)g * TBL_ENTRIES * 32;
-  jac acc = r ? jac_mul_small(P, r * TBL_ENTRIES + 1) : P;
+  uint32_t* sc = scratch + (size_t)g * FB_ENTRIES * 32;
+  jac acc = r ? jac_mul_small(P, r * FB_ENTRIES + 1) : P;
   fp prod = fp_one();
-  for (int k = 0; k < TBL_ENTRIES; ++k) {
+  for (int k = 0; k < FB_ENTRIES; ++k) {
     st_jac(sc + 32 * k, acc);
     st_fp(sc + 32 * k + 24, prod);  // exclusive prefix product of the non-zero Z's before k
     if (!jac_is_inf(acc)) prod = fp_mul(prod, acc.z);
@@ -168,7 +135,7 @@ extern "C" __global__ void __launch_bounds__(64) k_fb_table(const uint32_t* base
   fp inv = fp_inv(prod);  // Montgomery's trick: one inversion per run
   const int outer = b / inner, in = b % inner;
   uint32_t* dst0 = table + 16 * ((long long)outer * s_outer + (long long)e0 * s_e + (long long)in * s_in);
-  for (int k = TBL_ENTRIES - 1; k >= 0; --k) {
+  for (int k = FB_ENTRIES - 1; k >= 0; --k) {
     jac pt = ld_jac(sc + 32 * k);
     aff o;
     if (jac_is_inf(pt)) {
@@ -221,38 +188,15 @@ __device__ __forceinline__ void shares_msm_body(const long long* coeffs, int d, 
   else BSC_SET_PRIO(BSC_PRIO_SPEC);
   const int S = commit_only == 1 ? 1 : T + 1;   // output slots per (row, chunk)
   const int SL = commit_only == 2 ? T : S;      // lanes per (row, chunk)
-  // compact (optional): [count, row...] -- only the listed rows are computed, packed densely over the
-  // grid (a rejected row costs no SIMD lanes); the grid is sized for nrows, the surplus exits at once
+  // 1. map the lane (msm_lanes.h).  compact (optional): [count, row...] -- only the listed rows are computed,
+  // packed densely over the grid (a rejected row costs no SIMD lanes); the grid is sized for nrows, the
+  // surplus exits at once
   const int neff = compact != nullptr ? compact[0] : nrows;
-  const long long total = (long long)neff * nchunks * SL;
-  // group_rows G > 0: rows are taken G at a time in list order (the speculative rows arrive sorted
-  // by their arrival at the leader), chunk-major inside a group, and the XCD remap is applied per
-  // 64-block super-block -- so work proceeds through the row list in dispatch order (rows the
-  // selection drops later are skipped when reached) while each XCD still shares a chunk's table
-  // lines across the group's rows.  G = 0: one group of every row, remapped over the whole grid.
-  int lb;
-  if (group_rows > 0) {
-    const int SB = 64;
-    const int q = blockIdx.x / SB, j = blockIdx.x % SB;
-    const int sbn = min(SB, (int)gridDim.x - q * SB);
-    lb = q * SB + xcd_remap(j, sbn);
-  } else {
-    lb = xcd_remap(blockIdx.x, gridDim.x);
-  }
-  const long long g = (long long)lb * blockDim.x + threadIdx.x;
-  if (g >= total) return;
-  const int G = group_rows > 0 ? min(group_rows, neff) : neff;
-  const long long per_group = (long long)G * nchunks * SL;
-  const int gq = (int)(g / per_group);
-  const int r0 = gq * G, gr = min(G, neff - r0);
-  const long long gg = g - (long long)gq * per_group;
-  // chunk-major inside the group: consecutive groups of SL lanes share a chunk (and its table lines)
-  const int slot = (int)(gg % SL);
-  const long long grp = gg / SL;
-  const int pos = r0 + (int)(grp % gr);
-  const int r = compact != nullptr ? compact[1 + pos] : pos;
-  const int k = (int)(grp / gr);
-  // late cancellation of speculative work: rows the verifiers rejected (flag cleared by
+  const ShareLane lane = share_lane(blockIdx.x, threadIdx.x, gridDim.x, neff, nchunks, SL, group_rows);
+  if (lane.none) return;
+  const int k = lane.k, slot = lane.slot;
+  const int r = compact != nullptr ? compact[1 + lane.pos] : lane.pos;
+  // 2. late cancellation of speculative work: rows the verifiers rejected (flag cleared by
   // k_set_alive on the critical-path stream while this kernel runs) are skipped from then on;
   // their outputs are never read.  A stale read only costs the work.
   if (alive != nullptr && __hip_atomic_load(alive + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
@@ -263,19 +207,16 @@ __device__ __forceinline__ void shares_msm_body(const long long* coeffs, int d, 
   const int J = poly - 1;
   const long long* c = coeffs + (size_t)row * d + prev;
 
-  const int E0 = 1 << (B0 - 1);
-  const size_t PB = (size_t)E0 + (size_t)(NW - 1) * TBL_ENTRIES;
-  const size_t pk_base_stride = PB * 16;
-  const size_t wb_j_stride = PB * T * 16;
+  const FbPlan plan = fb_plan(B0, NW);
+  const size_t pk_base_stride = (size_t)plan.PB * 16;
+  const size_t wb_j_stride = (size_t)plan.PB * T * 16;
   const uint32_t* wb_chunk = tbl_wb + (size_t)k * J * wb_j_stride;
 
+  // 3. accumulate: the commitment uses c_0..c_{L-1} on PK[prev..]; a witness c_1..c_{L-1} on B_{1..L-1, x}
   jac acc = jac_inf();
-  // commitment uses c_0..c_{L-1} on PK[prev..]; witness uses c_1..c_{L-1} on B_{1..L-1, x}
   for (int j = is_commit ? 0 : 1; j < L; ++j) {
     const long long cj = c[j];
     if (cj == 0) continue;
-    const bool neg = cj < 0;
-    unsigned long long m = neg ? 0ull - (unsigned long long)cj : (unsigned long long)cj;
     const uint32_t* tb;
     size_t estride;
     if (is_commit) {
@@ -285,16 +226,13 @@ __device__ __forceinline__ void shares_msm_body(const long long* coeffs, int d, 
       tb = wb_chunk + (size_t)(j - 1) * wb_j_stride + (size_t)slot * 16;
       estride = (size_t)T * 16;
     }
-    int carry = 0;
-    for (int w = 0; w < NW && (m != 0 || carry != 0); ++w) {
-      const int dg = recode(m, carry, win_bits(w, B0));
-      if (dg == 0) continue;
-      const int ad = dg < 0 ? -dg : dg;
-      aff q = ld_aff(tb + (size_t)win_entry(w, ad, E0) * estride);
-      if ((dg < 0) != neg) q = aff_neg(q);
+    fb_walk(cj, plan, [&](int w, int ad, bool negate) {
+      aff q = ld_aff(tb + (size_t)fb_entry(plan, w, ad) * estride);
+      if (negate) q = aff_neg(q);
       acc = jac_add_aff(acc, q);
-    }
+    });
   }
+  // 4. store (+ the share value)
   const size_t o = ((size_t)r * nchunks + k) * S + slot;
   st_jac(out_pts + 24 * o, acc);
   if (!is_commit && out_y != nullptr) {
@@ -306,7 +244,7 @@ __device__ __forceinline__ void shares_msm_body(const long long* coeffs, int d, 
   }
 }
 
-extern "C" __global__ void __launch_bounds__(256) k_shares_msm(
+extern "C" __global__ void __launch_bounds__(SHARE_MSM_THREADS) k_shares_msm(
     const long long* coeffs, int d, const int* rows, int nrows, const uint32_t* tbl_pk, const uint32_t* tbl_wb,
     int poly, int T, int B0, int NW, int commit_only, const int* alive, const int* compact, int group_rows,
     uint32_t* out_pts, long long* out_y) {
@@ -314,7 +252,7 @@ extern "C" __global__ void __launch_bounds__(256) k_shares_msm(
                   group_rows, out_pts, out_y);
 }
 
-extern "C" __global__ void __launch_bounds__(256) k_shares_msm_ka(
+extern "C" __global__ void __launch_bounds__(SHARE_MSM_THREADS) k_shares_msm_ka(
     const long long* coeffs, int d, RowArg rows, int nrows, const uint32_t* tbl_pk, const uint32_t* tbl_wb,
     int poly, int T, int B0, int NW, int commit_only, const int* alive, int group_rows, uint32_t* out_pts,
     long long* out_y) {
@@ -343,24 +281,17 @@ extern "C" __global__ void __launch_bounds__(256) k_commit_rows(const long long*
   if (r >= nrows) return;  // uniform per block
   const long long* c = coeffs + (size_t)rows[r] * d;
   const int c0 = slab * COMMIT_CB, c1 = min(d, c0 + COMMIT_CB);
-  const int E0 = 1 << (B0 - 1);
-  const size_t PB = (size_t)E0 + (size_t)(NW - 1) * TBL_ENTRIES;
+  const FbPlan plan = fb_plan(B0, NW);
   if (threadIdx.x == 0) cnt = 0;
   __syncthreads();
   for (int i = c0 + (int)threadIdx.x; i < c1; i += 256) {
     const long long cj = c[i];
     if (cj == 0) continue;
-    const bool neg = cj < 0;
-    unsigned long long m = neg ? 0ull - (unsigned long long)cj : (unsigned long long)cj;
-    int carry = 0;
-    for (int w = 0; w < NW && (m != 0 || carry != 0); ++w) {
-      const int dg = recode(m, carry, win_bits(w, B0));
-      if (dg == 0) continue;
-      const int ad = dg < 0 ? -dg : dg;
-      uint32_t e = (uint32_t)((size_t)i * PB + win_entry(w, ad, E0));
-      if ((dg < 0) != neg) e |= 0x80000000u;
+    fb_walk(cj, plan, [&](int w, int ad, bool negate) {
+      uint32_t e = (uint32_t)((size_t)i * (size_t)plan.PB + fb_entry(plan, w, ad));   // < 2^31 (bsc_commit_rows)
+      if (negate) e |= 0x80000000u;
       lds[atomicAdd(&cnt, 1)] = e;
-    }
+    });
   }
   __syncthreads();
   const int n = cnt;
@@ -381,11 +312,7 @@ extern "C" __global__ void __launch_bounds__(256) k_commit_rows(const long long*
   __syncthreads();
   st_jac(lds + threadIdx.x * 24, acc);
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      st_jac(lds + threadIdx.x * 24, jac_add(ld_jac(lds + threadIdx.x * 24), ld_jac(lds + (threadIdx.x + s) * 24)));
-    __syncthreads();
-  }
+  lds_tree_sum(lds, threadIdx.x, 256);
   if (threadIdx.x == 0) st_jac(out_partial + 24 * (size_t)b, ld_jac(lds));
 }
 
@@ -445,8 +372,7 @@ extern "C" __global__ void __launch_bounds__(64) k_chunk_check(const long long* 
   __shared__ int cnt;
   const int k = blockIdx.x, t = threadIdx.x;
   const int prev = k * poly, L = min(poly, d - prev);
-  const int E0 = 1 << (B0 - 1);
-  const size_t PB = (size_t)E0 + (size_t)(NW - 1) * TBL_ENTRIES;
+  const FbPlan plan = fb_plan(B0, NW);
   if (t == 0) cnt = 0;
   if (t < 16) {
     for (int w = 0; w < 9; ++w) dig[t][w] = 0;
@@ -456,7 +382,7 @@ extern "C" __global__ void __launch_bounds__(64) k_chunk_check(const long long* 
       unsigned long long m = neg ? 0ull - (unsigned long long)cj : (unsigned long long)cj;
       int carry = 0;
       for (int w = 0; w < NW && (m != 0 || carry != 0); ++w) {
-        const int dg = recode(m, carry, win_bits(w, B0));
+        const int dg = fb_next_digit(m, carry, fb_window_bits(plan, w));
         dig[t][w] = neg ? -dg : dg;
       }
     }
@@ -467,7 +393,7 @@ extern "C" __global__ void __launch_bounds__(64) k_chunk_check(const long long* 
     const int dg = w < NW ? dig[j][w] : 0;
     if (dg == 0) continue;
     const int ad = dg < 0 ? -dg : dg;
-    const uint32_t ent = (uint32_t)((size_t)(prev + j) * PB + win_entry(w, ad, E0));
+    const uint32_t ent = (uint32_t)((size_t)(prev + j) * (size_t)plan.PB + fb_entry(plan, w, ad));
     items[atomicAdd(&cnt, 1)] = ent | (dg < 0 ? 0x80000000u : 0u);
   }
   __syncthreads();
@@ -488,12 +414,7 @@ extern "C" __global__ void __launch_bounds__(64) k_chunk_check(const long long* 
   }
   st_jac(sh + t * 24, v);
   __syncthreads();
-  int p2 = 1;
-  while (p2 < m) p2 <<= 1;
-  for (int s = p2 >> 1; s > 0; s >>= 1) {
-    if (t < s) st_jac(sh + t * 24, jac_add(ld_jac(sh + t * 24), ld_jac(sh + (t + s) * 24)));
-    __syncthreads();
-  }
+  lds_tree_sum(sh, t, m);
   if (t < nm) {
     const int v = jac_equal(ld_jac(sh), ld_jac(csum + 24 * ((size_t)t * nch + k))) ? 1 : 0;
     ok[(size_t)t * nch + k] = v;
@@ -579,15 +500,7 @@ extern "C" __global__ void __launch_bounds__(256) k_segment_sum(const uint32_t* 
   st_jac(sh + threadIdx.x * 24, acc);
   __syncthreads();
   // tree only over the lanes that hold partial sums (n is typically 8 slabs: 3 levels, not 8)
-  int top = 1;
-  while (top < n && top < (int)blockDim.x) top <<= 1;
-  for (int s = top / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      jac a = ld_jac(sh + threadIdx.x * 24), b = ld_jac(sh + (threadIdx.x + s) * 24);
-      st_jac(sh + threadIdx.x * 24, jac_add(a, b));
-    }
-    __syncthreads();
-  }
+  lds_tree_sum(sh, threadIdx.x, min(n, (int)blockDim.x));
   if (threadIdx.x == 0) {
     const jac r = ld_jac(sh);
     st_jac(out + 24 * (size_t)g, r);
@@ -765,12 +678,7 @@ extern "C" __global__ void __launch_bounds__(64) k_block_commit_check(const uint
   }
   st_jac(sh + t * 24, acc);
   __syncthreads();
-  int top = 1;
-  while (top < n && top < 64) top <<= 1;
-  for (int s = top / 2; s > 0; s >>= 1) {
-    if (t < s) st_jac(sh + t * 24, jac_add(ld_jac(sh + t * 24), ld_jac(sh + (t + s) * 24)));
-    __syncthreads();
-  }
+  lds_tree_sum(sh, t, min(n, 64));
   if (t == 0) {
     if (bad != 0x7FFFFFFF) {
       status[r] = AUD_BAD_POINT;
@@ -810,26 +718,29 @@ extern "C" int bsc_witness_bases(const uint32_t* pk_aff, int d, int poly, int T,
 extern "C" int bsc_fb_table(const uint32_t* bases, int bases_are_jac, int b0, int nb, int inner, int B0, int NW,
                             long long s_outer, long long s_e, long long s_in, uint32_t* table, uint32_t* scratch,
                             void* stream) {
-  if (B0 < 8 || B0 > 20 || NW < 1) return -1;
-  const long long runs = (1ll << (B0 - 1)) / TBL_ENTRIES + NW - 1;
-  const long long n = (long long)nb * runs;
+  if (!fb_plan_ok(B0, NW)) return -1;
+  const long long n = (long long)nb * fb_runs(fb_plan(B0, NW));
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_fb_table, dim3(blocks_for(n, 64)), dim3(64), 0, (hipStream_t)stream, bases, bases_are_jac, b0,
                      nb, inner, B0, NW, s_outer, s_e, s_in, table, scratch);
   return (int)hipGetLastError();
 }
 
+// Entries per base of a (B0, NW) table, -1 for a plan bsc_fb_table refuses: whoever allocates a table checks
+// its own size formula against this one before the first launch (ops/bn256.py fb_entries).
+extern "C" int bsc_fb_entries(int B0, int NW) { return fb_plan_ok(B0, NW) ? (int)fb_plan(B0, NW).PB : -1; }
+
 extern "C" int bsc_shares_msm(const long long* coeffs, int d, const int* rows, int nrows, const uint32_t* tbl_pk,
                               const uint32_t* tbl_wb, int poly, int T, int B0, int NW, int commit_only,
                               const int* alive, const int* compact, int group_rows, uint32_t* out_pts,
                               long long* out_y, void* stream) {
-  if (B0 < 8 || B0 > 20 || B0 + 8 * (NW - 1) < 65) return -1;  // every int64 scalar must be covered
+  if (!fb_covers_i64(B0, NW)) return -1;
   if (commit_only < 0 || commit_only > 2) return -1;
   const int nchunks = (d + poly - 1) / poly;
   const int SL = commit_only == 1 ? 1 : commit_only == 2 ? T : T + 1;
   const long long n = (long long)nrows * nchunks * SL;
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_shares_msm, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, coeffs, d, rows,
+  hipLaunchKernelGGL(k_shares_msm, dim3(blocks_for(n, SHARE_MSM_THREADS)), dim3(SHARE_MSM_THREADS), 0, (hipStream_t)stream, coeffs, d, rows,
                      nrows, tbl_pk, tbl_wb, poly, T, B0, NW, commit_only, alive, compact, group_rows, out_pts,
                      out_y);
   return (int)hipGetLastError();
@@ -839,7 +750,7 @@ extern "C" int bsc_shares_msm(const long long* coeffs, int d, const int* rows, i
 extern "C" int bsc_shares_msm_ka(const long long* coeffs, int d, const int* rows_host, int nrows, const uint32_t* tbl_pk,
                                  const uint32_t* tbl_wb, int poly, int T, int B0, int NW, int commit_only,
                                  const int* alive, int group_rows, uint32_t* out_pts, long long* out_y, void* stream) {
-  if (B0 < 8 || B0 > 20 || B0 + 8 * (NW - 1) < 65) return -1;
+  if (!fb_covers_i64(B0, NW)) return -1;
   if (commit_only < 0 || commit_only > 2 || nrows > ROWARG_MAX || nrows < 0) return -1;
   const int nchunks = (d + poly - 1) / poly;
   const int SL = commit_only == 1 ? 1 : commit_only == 2 ? T : T + 1;
@@ -847,7 +758,7 @@ extern "C" int bsc_shares_msm_ka(const long long* coeffs, int d, const int* rows
   if (n <= 0) return 0;
   RowArg ra;
   for (int i = 0; i < nrows; ++i) ra.r[i] = rows_host[i];
-  hipLaunchKernelGGL(k_shares_msm_ka, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, coeffs, d, ra,
+  hipLaunchKernelGGL(k_shares_msm_ka, dim3(blocks_for(n, SHARE_MSM_THREADS)), dim3(SHARE_MSM_THREADS), 0, (hipStream_t)stream, coeffs, d, ra,
                      nrows, tbl_pk, tbl_wb, poly, T, B0, NW, commit_only, alive, group_rows, out_pts, out_y);
   return (int)hipGetLastError();
 }
@@ -921,9 +832,8 @@ extern "C" int bsc_sum_cols_serial(const uint32_t* pts, int ncols_in, int nrows,
 extern "C" int bsc_commit_rows(const long long* coeffs, int d, const int* rows, int nrows, const uint32_t* tbl_pk,
                                int B0, int NW, uint32_t* partial, uint32_t* out, void* stream) {
   if (nrows <= 0) return 0;
-  if (B0 < 8 || B0 > 20 || B0 + 8 * (NW - 1) < 65 || NW > 9) return -1;
-  const long long PB = (1ll << (B0 - 1)) + (long long)(NW - 1) * TBL_ENTRIES;
-  if ((long long)d * PB >= (1ll << 31)) return -1;
+  if (!fb_covers_i64(B0, NW) || NW > 9) return -1;   // NW <= 9: the slab's work list holds 9 digits per coefficient
+  if ((long long)d * fb_plan(B0, NW).PB >= (1ll << 31)) return -1;   // the work list's 31-bit entry index
   const int nslab = (d + COMMIT_CB - 1) / COMMIT_CB;
   hipLaunchKernelGGL(k_commit_rows, dim3(nrows * nslab), dim3(256), 0, (hipStream_t)stream, coeffs, d, rows, nrows,
                      tbl_pk, B0, NW, partial);
@@ -944,7 +854,7 @@ extern "C" int bsc_segment_sum(const uint32_t* pts, int ngroups, int n, int stri
 extern "C" int bsc_chunk_check(const long long* coeffs, int d, int poly, const uint32_t* tbl_pk, int B0, int NW,
                                const uint32_t* csum, int nm, int nch, int* ok, int* h_ok, void* stream) {
   if (nch <= 0 || nm <= 0) return 0;
-  if (poly < 1 || poly > 16 || nm > 64 || B0 < 8 || B0 > 20 || B0 + 8 * (NW - 1) < 65 || NW > 9) return -1;
+  if (poly < 1 || poly > 16 || nm > 64 || !fb_covers_i64(B0, NW) || NW > 9) return -1;   // dig[16][9]
   if ((long long)nch * poly < d || (long long)(nch - 1) * poly >= d) return -1;
   hipLaunchKernelGGL(k_chunk_check, dim3(nch), dim3(64), 0, (hipStream_t)stream, coeffs, d, poly, tbl_pk, B0, NW,
                      csum, nm, nch, ok, h_ok);

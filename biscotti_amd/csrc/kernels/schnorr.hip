@@ -38,6 +38,7 @@
 #include <stdint.h>
 
 #include "bn256_dev.h"
+#include "fixed_base.h"
 
 using namespace bn;
 
@@ -47,6 +48,7 @@ constexpr int SP = 16;                // items per workgroup (one wave: 16 items
 constexpr int DRAWS = 32;             // candidate draws at most (16 output nodes): missed with 0.439^32 ~ 3.5e-12
 constexpr int SNW = 33;               // windows per base
 constexpr int SPB = SNW * 128;        // entries per base
+static_assert(SPB == fb_plan(8, SNW).PB, "the verifier's table is the (B0 = 8, NW = 33) plan of fixed_base.h");
 constexpr int HALF = 17;              // windows of a lane: 0..16, 17..32 (the second half has 16)
 
 typedef unsigned long long u64;

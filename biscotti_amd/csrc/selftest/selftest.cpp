@@ -5,6 +5,7 @@
 // jobs from several submitting threads, jobs that wait on earlier jobs), so memory errors, UB and data races
 // that the Python tests cannot see show up here.
 #include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <future>
@@ -12,9 +13,11 @@
 #include <vector>
 
 #include "bn256.hpp"
+#include "fixed_base.h"
 #include "hash.hpp"
 #include "keys.hpp"
 #include "ledger.hpp"
+#include "msm_lanes.h"
 #include "pairing.hpp"
 #include "pool.hpp"
 #include "protocol.hpp"
@@ -213,7 +216,102 @@ static void test_pool(int t) {
   CHECK(first.get() == 3ll * 299 * 300 / 2);
 }
 
+// The share MSM's lane map (kernels/msm_lanes.h), exhaustively: over every lane of the grid the kernel is
+// launched with, the lanes below neff * nchunks * SL hit every (pos, k, slot) exactly once and every other lane
+// reports `none` -- for the plain and the grouped order, a short last group, a list compacted to fewer rows than
+// the grid was sized for, and an empty list.
+static void test_share_lanes() {
+  for (int grid = 1; grid <= 130; ++grid) {
+    std::vector<char> seen(size_t(grid), 0);
+    for (int b = 0; b < grid; ++b) {
+      const int l = xcd_remap(b, grid);
+      CHECK(l >= 0 && l < grid && !seen[size_t(l)]);
+      if (l >= 0 && l < grid) seen[size_t(l)] = 1;
+    }
+  }
+  const int shapes[5][2] = {{70, 11}, {37, 6}, {248, 3}, {9, 30}, {1, 1}};
+  for (const auto& sh : shapes) {
+    const int nrows = sh[0], nchunks = sh[1];
+    for (int SL : {1, 21, 22}) {
+      const int grid = int(((long long)nrows * nchunks * SL + SHARE_MSM_THREADS - 1) / SHARE_MSM_THREADS);
+      for (int group_rows : {0, 1, 8, 35, nrows + 5}) {
+        for (int neff : {nrows, nrows - 3, 1, 0}) {
+          if (neff < 0) continue;
+          const long long total = (long long)neff * nchunks * SL;
+          std::vector<char> seen(size_t(total), 0);
+          long long hit = 0, bad = 0;
+          for (int b = 0; b < grid; ++b)
+            for (int t = 0; t < SHARE_MSM_THREADS; ++t) {
+              const ShareLane l = share_lane(b, t, grid, neff, nchunks, SL, group_rows);
+              if (l.none) continue;
+              if (l.pos < 0 || l.pos >= neff || l.k < 0 || l.k >= nchunks || l.slot < 0 || l.slot >= SL) {
+                ++bad;
+                continue;
+              }
+              char& s = seen[(size_t(l.pos) * size_t(nchunks) + size_t(l.k)) * size_t(SL) + size_t(l.slot)];
+              bad += s;
+              s = 1;
+              ++hit;
+            }
+          CHECK(bad == 0);
+          CHECK(hit == total);   // with no repeats: every (pos, k, slot) once, every other lane `none`
+        }
+      }
+    }
+  }
+}
+
+// The fixed-base window plan (kernels/fixed_base.h): the entries of all (window, |digit|) tile [0, PB) exactly,
+// and the signed-digit recoding rebuilds the scalar from digits inside each window's table.
+static void test_fixed_base_plan() {
+  const int plans[5][2] = {{8, 9}, {9, 8}, {11, 8}, {14, 8}, {8, 33}};   // NW = windows_for(B0); the Schnorr plan
+  for (const auto& pl : plans) {
+    const int B0 = pl[0], NW = pl[1];
+    CHECK(fb_plan_ok(B0, NW));
+    CHECK(fb_covers_i64(B0, NW));
+    if (NW < 33) CHECK(NW == 1 + (65 - B0 + 7) / 8 && !fb_covers_i64(B0, NW - 1));
+    const FbPlan p = fb_plan(B0, NW);
+    CHECK(p.E0 == 1 << (B0 - 1) && p.PB == (long long)fb_runs(p) * FB_ENTRIES);
+    std::vector<char> seen(size_t(p.PB), 0);
+    long long n = 0;
+    for (int w = 0; w < NW; ++w)
+      for (int ad = 1; ad <= 1 << (fb_window_bits(p, w) - 1); ++ad, ++n) {
+        const int e = fb_entry(p, w, ad);
+        CHECK(e >= 0 && e < p.PB && !seen[size_t(e)]);
+        if (e >= 0 && e < p.PB) seen[size_t(e)] = 1;
+      }
+    CHECK(n == p.PB);   // distinct and as many as the table has: [0, PB) exactly
+    const long long half = 1ll << (B0 - 1);
+    const long long cs[] = {0, 1, -1, half, -half, half + 1, -(half + 1), INT64_MAX, INT64_MIN};
+    for (const long long c : cs) {
+      // the primitives, as k_chunk_check uses them
+      unsigned long long m = c < 0 ? 0ull - (unsigned long long)c : (unsigned long long)c;
+      int carry = 0;
+      __int128 sum = 0;
+      for (int w = 0; w < NW; ++w) {
+        const int bits = fb_window_bits(p, w);
+        const int dg = fb_next_digit(m, carry, bits);
+        CHECK(dg > -(1 << (bits - 1)) && dg <= 1 << (bits - 1));
+        if (dg != 0) sum += (__int128)dg * ((__int128)1 << fb_window_shift(p, w));   // nonzero only below 2^72
+      }
+      CHECK(m == 0 && carry == 0);
+      CHECK(sum == (c < 0 ? -(__int128)c : (__int128)c));
+      // the walk, as the share and row MSMs use it
+      __int128 walked = 0;
+      fb_walk(c, p, [&](int w, int ad, bool negate) {
+        CHECK(w >= 0 && w < NW && ad >= 1 && ad <= 1 << (fb_window_bits(p, w) - 1));
+        const __int128 term = (__int128)ad << fb_window_shift(p, w);
+        walked += negate ? -term : term;
+      });
+      CHECK(walked == (__int128)c);
+    }
+  }
+  CHECK(!fb_plan_ok(7, 9) && !fb_plan_ok(21, 9) && !fb_plan_ok(8, 0) && !fb_covers_i64(14, 7));
+}
+
 int main(int argc, char** argv) {
+  test_share_lanes();   // the kernels' host-checkable headers (pure functions), in either mode
+  test_fixed_base_plan();
   if (argc > 1 && std::strcmp(argv[1], "pool") == 0) {
     // the concurrency stress alone (ThreadSanitizer runs: the crypto modules are ~10x slower under it)
     std::vector<std::thread> ts;
@@ -222,6 +320,8 @@ int main(int argc, char** argv) {
     std::printf("selftest pool: %s (%d failures)\n", failures ? "FAILED" : "ok", failures.load());
     return failures ? 1 : 0;
   }
+  test_share_lanes();   // (repeated in the full run: milliseconds)
+  test_fixed_base_plan();
   // run every module twice on 6 threads concurrently (lazy statics, caches and tables included)
   std::vector<std::thread> ts;
   for (int t = 0; t < 6; ++t)

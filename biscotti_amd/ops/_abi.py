@@ -16,6 +16,7 @@ SIGNATURES = {
     "bsc_point_op": [P, P, P, P, I, I, P],
     "bsc_witness_bases": [P, I, I, I, P, P],
     "bsc_fb_table": [P, I, I, I, I, I, I, L, L, L, P, P, P],
+    "bsc_fb_entries": [I, I],
     "bsc_shares_msm": [P, I, P, I, P, P, I, I, I, I, I, P, P, I, P, P, P],
     "bsc_shares_msm_ka": [P, I, P, I, P, P, I, I, I, I, I, P, I, P, P, P],
     "bsc_alive_compact": [P, I, P, P],

@@ -21,10 +21,26 @@ B0_CHOICES = (14, 13, 12, 11, 10, 9, 8)   # first-window widths, widest that fit
 _SCRATCH_BYTES = 1 << 31
 
 
+def fb_entries(b0: int, nw: int) -> int:
+    """Entries per base of a fixed-base table: 2^(b0-1) of the first window, 128 per further window.  The one
+    Python copy of the window plan of csrc/kernels/fixed_base.h; whoever allocates a table checks it against
+    the library's bsc_fb_entries first (check_fb_entries)."""
+    return (1 << (b0 - 1)) + (nw - 1) * TBL_ENTRIES
+
+
+def check_fb_entries(b0: int, nw: int) -> int:
+    """fb_entries(b0, nw), after checking that the kernels index a table of exactly that size."""
+    pb, native = fb_entries(b0, nw), hip().bsc_fb_entries(b0, nw)
+    if native != pb:
+        raise RuntimeError(f"fixed-base plan (B0={b0}, NW={nw}): the library has {native} entries per base, "
+                           f"the table would be allocated with {pb}")
+    return pb
+
+
 def windows_for(b0: int) -> tuple[int, int]:
     """(NW, entries per base) for a B0-bit first window followed by 8-bit windows covering int64."""
     nw = 1 + -(-(65 - b0) // 8)
-    return nw, (1 << (b0 - 1)) + (nw - 1) * TBL_ENTRIES
+    return nw, fb_entries(b0, nw)
 
 
 def table_bytes_for(d: int, poly: int, total_shares: int, b0: int) -> int:
@@ -97,6 +113,7 @@ class DeviceCommitEngine:
         self.nw, self.pb = windows_for(self.b0)
         self.nchunks = (self.d + self.poly - 1) // self.poly
         lib = hip()
+        check_fb_entries(self.b0, self.nw)   # before the tables are allocated
         self.pk_aff = u32_tensor(commit_key.affine_mont_u32(), self.device)  # [d, 16]
         # witness bases B_{j,x}: [nchunks][J][T][24]
         self.wbases = torch.empty((self.nchunks, self.J, self.T, 24), dtype=torch.int32, device=self.device)
@@ -119,7 +136,7 @@ class DeviceCommitEngine:
 
     def _build_table(self, bases, jac: bool, nbases: int, inner: int, strides, table) -> None:
         lib = hip()
-        runs = (1 << (self.b0 - 1)) // TBL_ENTRIES + self.nw - 1   # 128-entry runs per base
+        runs = fb_entries(self.b0, self.nw) // TBL_ENTRIES   # 128-entry runs per base
         per_base = TBL_ENTRIES * 32 * 4 * runs
         batch = max(inner, (_SCRATCH_BYTES // per_base) // inner * inner)
         scratch = torch.empty((min(batch, nbases) * runs * TBL_ENTRIES * 32,), dtype=torch.int32, device=self.device)

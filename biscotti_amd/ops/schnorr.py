@@ -19,9 +19,10 @@ import torch
 from ..native import hip, rt
 from ..utils import d2h_into, h2d_many
 from ..utils import streams as S
+from .bn256 import check_fb_entries, fb_entries
 
 B0, NW = 8, 33
-PB = NW * 128            # entries per base
+PB = fb_entries(B0, NW)  # entries per base
 DRAWS = 32
 _BUILD_BATCH = 32        # bases per table-build launch: 33 runs x 16 KB of scratch each
 VALID, RANGE, MISMATCH, UNDECIDED, INDEX = 0, 1, 2, 3, 4
@@ -48,8 +49,9 @@ class SchnorrVerifier:
                                [R.g1_affine_mont_u32(k) for k in self.pks]).astype(np.uint32)   # [1 + N, 16]
         nb = 1 + self.nkeys
         bases_t = torch.from_numpy(np.ascontiguousarray(bases).view(np.int32)).to(self.device)
+        check_fb_entries(B0, NW)   # before the table is allocated
         self.table = torch.empty((nb, PB, 16), dtype=torch.int32, device=self.device)
-        scratch = torch.empty((min(_BUILD_BATCH, nb) * NW * 128 * 32,), dtype=torch.int32, device=self.device)
+        scratch = torch.empty((min(_BUILD_BATCH, nb) * PB * 32,), dtype=torch.int32, device=self.device)
         for s0 in range(0, nb, _BUILD_BATCH):
             _check(lib.bsc_fb_table(bases_t.data_ptr(), 0, s0, min(_BUILD_BATCH, nb - s0), 1, B0, NW, PB, 1, 0,
                                     self.table.data_ptr(), scratch.data_ptr(), S.raw()), "fb_table")

@@ -264,3 +264,19 @@ def test_sum_cols_serial_masked_witness_sums(rt):
                 assert bytes(g[i]) == wits[k * 21 + s]
         else:
             assert not B.marshal(got).cpu().numpy().any()   # infinity marshals as zeros
+
+
+def test_fb_entries_agree_with_the_library():
+    """The table size the Python side allocates (fb_entries) is the one the kernels index (bsc_fb_entries,
+    kernels/fixed_base.h), for every plan in use: the engine's first-window choices and the Schnorr verifier's
+    (8, 33).  A plan the table builder refuses has no size."""
+    from biscotti_amd.native import hip
+    from biscotti_amd.ops import bn256 as B
+    from biscotti_amd.ops import schnorr
+    plans = [(b0, B.windows_for(b0)[0]) for b0 in B.B0_CHOICES] + [(8, 33)]
+    assert (schnorr.B0, schnorr.NW) == (8, 33) and schnorr.PB == B.fb_entries(8, 33) == 33 * 128
+    for b0, nw in plans:
+        assert hip().bsc_fb_entries(b0, nw) == B.fb_entries(b0, nw) == B.check_fb_entries(b0, nw), (b0, nw)
+        assert B.windows_for(b0)[1] == B.fb_entries(b0, B.windows_for(b0)[0])
+    for b0, nw in [(7, 9), (21, 9), (8, 0)]:
+        assert hip().bsc_fb_entries(b0, nw) == -1, (b0, nw)

@@ -91,6 +91,56 @@ def test_kzg_literal_single_chunk(rt):
     assert rt.kzg_check_device_async(out.cpu().numpy().view(np.uint32), g2, rt.g2_mul(g2, 2)).result()
 
 
+def _extreme_ys(npts):
+    """int64 [6, npts], one pattern per chunk: two stacked triples of a three-chunk key.  With r odd and 64 bits
+    wide every product r * y carries through all three limbs of the 192-bit sum, with either sign."""
+    hi, lo = np.iinfo(np.int64).max, np.iinfo(np.int64).min
+    ys = np.empty((6, npts), dtype=np.int64)   # integers throughout: a float64 on the way would round 2^63 - 1
+    ys[0], ys[1], ys[3], ys[4], ys[5] = hi, lo, 0, -1, 1
+    ys[2, 0::2], ys[2, 1::2] = hi, lo
+    assert ys[0, 0] == 2**63 - 1 and ys[1, 0] == -2**63 and ys[2, 1] == -2**63 and ys[2, 2] == 2**63 - 1
+    return ys
+
+
+def test_kzg_extreme_share_values_match_host(rt):
+    """Share values at the ends of int64 (the fixtures elsewhere stay below 2^40): the signed 192-bit sums
+    Z_k = sum_j r_kj y_kj of the aggregate kernel and of the row kernel against the host's I192, byte for byte
+    in the marshalled (L1, A, L2).  d = 21: three chunks, the last of length 1 (its witnesses are infinity)."""
+    from biscotti_amd.ops.bn256 import kzg_row_seed
+    seed, npts = 0xC0FFEE1234, T
+    key, eng, csum, wsum, _, xs, spm = _aggregate(rt, 21, 2, [0, 1, 2], {0: 0, 1: 1, 2: 2}, seed=3)
+    nch = eng.nchunks
+    assert nch == 3 and xs.numel() == npts
+    ys = _extreme_ys(npts)
+    dev = lambda t: [rt.g1_from_device_jac(r) for r in t.cpu().numpy().view(np.uint32).reshape(-1, 24)]
+    bases = [key.point(POLY * k) for k in range(nch)]
+    x = xs.cpu().numpy().tolist()
+
+    # the aggregate kernel over the two triples stacked as six chunks ((chunk, point) order, spm = npts)
+    w = wsum.index_select(0, eng.kzg_order(npts, spm))
+    cs2, w2 = csum.repeat(2, 1), w.repeat(2, 1)
+    out = eng.kzg_rlc(cs2, w2, torch.from_numpy(ys).cuda(), xs.repeat(2), npts, literal=False, seed=seed)
+    got = dev(out)
+    assert got == list(rt.kzg_rlc_host(dev(cs2), dev(w2), ys.reshape(-1), x, bases * 2, seed, 4))
+
+    # the row kernel: two rows of shares, row i with triple i as its share values
+    coeffs = np.random.default_rng(5).integers(-10**6, 10**6, size=(2, 21), dtype=np.int64)
+    pts, _ = eng.shares(torch.from_numpy(coeffs).cuda(), torch.arange(2, dtype=torch.int32, device="cuda"))
+    yrows = torch.from_numpy(ys.reshape(2, nch, npts)).cuda()
+    assert xs.cpu().numpy().tolist() == list(range(-10, 11))   # the columns below are slots 0..20 in order
+    cols = torch.arange(npts, dtype=torch.int32, device="cuda")
+    rows = eng.kzg_rlc_rows(pts, yrows, cols, xs, seed=seed).cpu().numpy().view(np.uint32)
+    P = pts.cpu().numpy().view(np.uint32)
+    tot = None
+    for i in range(2):
+        C = [rt.g1_from_device_jac(P[i, k, T]) for k in range(nch)]
+        W = [rt.g1_from_device_jac(P[i, k, j]) for k in range(nch) for j in range(npts)]
+        want = tuple(rt.kzg_rlc_host(C, W, ys[3 * i:3 * i + 3].reshape(-1), x, bases, kzg_row_seed(seed, i), 4))
+        assert tuple(rt.g1_from_device_jac(p) for p in rows[i]) == want, f"row {i}"
+        tot = want if tot is None else tuple(rt.g1_add(a, b) for a, b in zip(tot, want))
+    assert tuple(rt.g1_from_device_jac(p) for p in rows[2]) == tot
+
+
 @pytest.mark.parametrize("mode", ["consistent", "literal"])
 def test_engine_kzg_audit_on_gpu(mode):
     """The engine's per-round KZG audit on the device path (MNIST, 785 chunks x 21 points per round):

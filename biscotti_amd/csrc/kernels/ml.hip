@@ -1276,7 +1276,8 @@ extern "C" __global__ void __launch_bounds__(LC_ROWS) k_logit_counts(const doubl
 // ys: int64 [nchunks][npts], xs: int [npts] distinct; deg+1 <= npts.  Newton divided differences
 // in 128-bit on the deg+1 nodes of smallest |x|, verified against every share.  Writes the
 // dequantised aggregate into W_new = W + coeff / 10^prec  (fp64, the reference's mat.Dense.Add).
-// status[k] = 1 exact, 0 inconsistent shares (caller falls back to least squares).
+// status[k] = 1 exact, 0 inconsistent shares, equal x-points or a coefficient outside int64 -- the cases in
+// which the host's recover_exact returns false (caller falls back to least squares).
 // =====================================================================================
 namespace {
 __device__ __forceinline__ bool div_small(__int128 a, long long d, __int128* q) {
@@ -1332,8 +1333,10 @@ extern "C" __global__ void k_recover(const long long* ys, int nchunks, int npts,
   }
   for (int lvl = 1; lvl < n && ok; ++lvl)
     for (int i = n - 1; i >= lvl && ok; --i) {
-      __int128 q;
-      ok = div_small(dd[i] - dd[i - 1], (long long)(nx[i] - nx[i - lvl]), &q);
+      __int128 q = 0;
+      const long long dx = (long long)(nx[i] - nx[i - lvl]);
+      // two equal x-points: no polynomial through them (the host's recover_exact returns false)
+      ok = dx != 0 && div_small(dd[i] - dd[i - 1], dx, &q);
       dd[i] = q;
     }
   if (ok) {
@@ -1345,6 +1348,8 @@ extern "C" __global__ void k_recover(const long long* ys, int nchunks, int npts,
       c[0] = -nx[kk] * c[0] + dd[kk];
       ++cur;
     }
+    // a coefficient outside int64 is no recovery (recover_exact returns false): the cast below would wrap it
+    for (int j = 0; j < n; ++j) ok = ok && c[j] >= (__int128)INT64_MIN && c[j] <= (__int128)INT64_MAX;
     for (int pt = 0; pt < npts && ok; ++pt) {
       __int128 acc = 0;
       for (int j = n - 1; j >= 0; --j) acc = acc * xs[pt] + c[j];
@@ -1417,6 +1422,8 @@ extern "C" __global__ void __launch_bounds__(256) k_recover_w(
     // a true coefficient is tiny next to 2^100; an inexact division lands anywhere in 2^128
     const __int128 lim = ((__int128)1) << 100;
     exact = exact && q < lim && q > -lim;
+    // and one outside int64 is no recovery (the host's recover_exact returns false): the cast in step 4 would wrap it
+    exact = exact && q >= (__int128)INT64_MIN && q <= (__int128)INT64_MAX;
     cf[c][j] = q;
     if (!exact) atomicAnd(&ok[c], 0);
   }

@@ -7,6 +7,11 @@
 // and c == H(marshal(r G + c PK) || message), H = the first BLAKE2Xb candidate v with 0 < v < n, the XOF keyed
 // with the 64-byte marshal of T = r G + c PK.
 //
+// Signing (k_schnorr_sign; the host signer schnorr_sign / run_sign_job is the specification): the nonce v is the
+// first candidate of the same XOF keyed with 36 bytes of entropy (the signer's nonce base || le32(nonce id)) and
+// given no message; T = v G, c = H(marshal(T) || message), r = v - sk c mod n.  One fixed-base product where the
+// verifier has two; the same 64 bytes as the host.  Its statuses: 0 signed | 3 | 4, as below.
+//
 // Status of an item (msg_idx, key_idx, signature), the first failing check decides:
 //   0 valid | 1 c >= n or r >= n | 2 the recomputed challenge differs | 3 undecided after DRAWS candidates (the
 //   host decides) | 4 msg_idx or key_idx out of range
@@ -34,6 +39,13 @@
 //  * There are no per-thread arrays with a run-time bound or a run-time index: the scalars' bytes are read from
 //    LDS, the BLAKE2b state and message words are named by literals.  The draw loop is bounded by DRAWS.
 //  * A wrong answer comes out as a status, never as an access outside a buffer.
+//  * The signer (k_schnorr_sign): msg_idx and key_idx are compared against nmsg / nkeys before a message, a key
+//    row or a nonce base is addressed; an out-of-range item reads only its own three index words.  The nonce is a
+//    XOF candidate, so it lies in (0, n) and recodes inside the table like a checked scalar; it reads base 0 only,
+//    windows 0..8 | 9..16 | 17..24 | 25..32 per lane (window_sum's guard w < SNW holds for any split).  The nonce's
+//    bytes come from LDS, the CIOS limbs and the BLAKE2b words are named by literals; both draw loops are the one
+//    loop bounded by DRAWS.  Every thread walks both barriers: an item that is out of range or found no nonce
+//    stores the point at infinity and its lane 0 writes a status (4 or 3) and 64 zero bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -117,9 +129,15 @@ __device__ __forceinline__ void b2_compress(u64 (&h)[8], const u64 (&m)[8], u64 
 //   output node i: digest 64, key 0, fanout 0, depth 0, leaf length 64, node offset i, bytes 12..15 = 0xFF, inner
 //                length 64; input the root digest, final (t = 64)
 //   candidate j: bytes 32 (j mod 2) .. +31 of node j div 2, big-endian
+// The signer's nonce (schnorr_nonce) is the same XOF keyed with 36 bytes of entropy and given no message: its root
+// node is the key block alone, final (t = 128), under a parameter block whose key length is 36.
 // One rolled loop holds the single inlined copy of the compression: steps 0 and 1 are the root node's two
-// blocks, step 2 + i is output node i.
-__device__ int schnorr_challenge(const u64 (&key)[8], const u64 (&msg)[8], u64 (&out)[4]) {
+// blocks (step 1 is skipped when there is no message), step 2 + i is output node i.  p0: the first word of the
+// root's parameter block; key: the key block's first 64 bytes (the rest is zero).
+constexpr u64 XOF_KEY64 = 0x0000000001014040ull;   // digest 64, key 64, fanout 1, depth 1
+constexpr u64 XOF_KEY36 = 0x0000000001012440ull;   // digest 64, key 36, fanout 1, depth 1
+__device__ __forceinline__ int schnorr_xof(u64 p0, const u64 (&key)[8], bool has_msg, const u64 (&msg)[8],
+                                           u64 (&out)[4]) {
   u64 st[8], root[8], m[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) root[i] = 0;
@@ -134,10 +152,10 @@ __device__ int schnorr_challenge(const u64 (&key)[8], const u64 (&msg)[8], u64 (
         st[i] = B2IV[i];
         m[i] = key[i];
       }
-      st[0] ^= 0x0000000001014040ull;
+      st[0] ^= p0;
       st[1] ^= 0xFFFFFFFF00000000ull;
       t = 128;
-      last = false;
+      last = !has_msg;
     } else if (step == 1) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) m[i] = msg[i];
@@ -160,6 +178,7 @@ __device__ int schnorr_challenge(const u64 (&key)[8], const u64 (&msg)[8], u64 (
       last = true;
     }
     b2_compress(st, m, t, last);
+    if (step == 0 && !has_msg) step = 1;   // the root node was that one block
     if (step >= 2) {
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
@@ -184,6 +203,9 @@ __device__ int schnorr_challenge(const u64 (&key)[8], const u64 (&msg)[8], u64 (
     }
   }
   return used;
+}
+__device__ __forceinline__ int schnorr_challenge(const u64 (&key)[8], const u64 (&msg)[8], u64 (&out)[4]) {
+  return schnorr_xof(XOF_KEY64, key, true, msg, out);
 }
 
 // ---------------------------------------------------------------- scalars and points
@@ -218,6 +240,30 @@ __device__ __forceinline__ int recode8(int byte, int& carry) {
   return d;
 }
 
+// One lane's share of a fixed-base product: the sum over windows w0 .. min(w0 + cnt, SNW) - 1 of digit(w) * 2^(8 w)
+// * base.  sc: the scalar's eight little-endian limbs in LDS (a run-time index is a plain address there); tb: the
+// base's SPB entries of 16 words.  The carry into w0 comes from recoding the windows below it.
+__device__ __forceinline__ jac window_sum(const uint32_t* sc, const uint32_t* __restrict__ tb, int w0, int cnt) {
+  jac acc = jac_inf();
+  int carry = 0;
+  for (int w = 0; w < w0; ++w) (void)recode8((int)(sc[w >> 2] >> (8 * (w & 3))), carry);   // the carry into w0
+#pragma unroll 1
+  for (int j = 0; j < cnt; ++j) {
+    const int w = w0 + j;
+    if (w < SNW) {                                 // w in [0, 32]
+      const int byte = w < 32 ? (int)((sc[w >> 2] >> (8 * (w & 3))) & 0xffu) : 0;
+      const int d = recode8(byte, carry);          // [-127, 128]; window 32: 0 or 1
+      if (d != 0) {
+        const int ad = d < 0 ? -d : d;             // [1, 128]
+        aff e = ld_aff(tb + 16 * (w * 128 + ad - 1));   // entry in [0, SPB)
+        if (d < 0) e = aff_neg(e);
+        acc = jac_add_aff(acc, e);
+      }
+    }
+  }
+  return acc;
+}
+
 // Phases 0 and 1 of the verifier and of bsc_schnorr_point, called by every thread of the workgroup (two barriers).
 // act: this lane's item takes part (the four lanes of an item agree); r / c: its scalars (little-endian limbs);
 // key: its peer key index, already checked to lie in [0, nkeys) when act.  On return s_part[q][p] holds lane
@@ -234,25 +280,7 @@ __device__ __forceinline__ void partial_sums(bool act, const uint32_t (&r)[8], c
   if (act) {
     const int which = q >> 1;                        // 0: r G, 1: c PK
     const long long base = which ? (long long)key + 1 : 0;
-    const uint32_t* tb = table + 16 * base * SPB;    // this base's SPB entries of 16 words
-    const uint32_t* sc = &s_sc[p][which][0];         // LDS: a run-time index is a plain address here
-    const int w0 = (q & 1) ? HALF : 0;
-    int carry = 0;
-    for (int w = 0; w < w0; ++w) (void)recode8((int)(sc[w >> 2] >> (8 * (w & 3))), carry);   // the carry into w0
-#pragma unroll 1
-    for (int j = 0; j < HALF; ++j) {
-      const int w = w0 + j;
-      if (w < SNW) {                                 // w in [0, 32]
-        const int byte = w < 32 ? (int)((sc[w >> 2] >> (8 * (w & 3))) & 0xffu) : 0;
-        const int d = recode8(byte, carry);          // [-127, 128]; window 32: 0 or 1
-        if (d != 0) {
-          const int ad = d < 0 ? -d : d;             // [1, 128]
-          aff e = ld_aff(tb + 16 * (w * 128 + ad - 1));   // entry in [0, SPB)
-          if (d < 0) e = aff_neg(e);
-          acc = jac_add_aff(acc, e);
-        }
-      }
-    }
+    acc = window_sum(&s_sc[p][which][0], table + 16 * base * SPB, (q & 1) ? HALF : 0, HALF);
   }
   st_jac(&s_part[q][p][0], acc);
   __syncthreads();
@@ -283,6 +311,96 @@ __device__ __forceinline__ void st_words64(uint32_t* p, const u64 (&m)[8]) {
     p[2 * i] = (uint32_t)m[i];
     p[2 * i + 1] = (uint32_t)(m[i] >> 32);
   }
+}
+
+// ---------------------------------------------------------------- the signer's scalars (mod n)
+constexpr uint32_t ORD_N0INV = 0x2d284e5fu;   // -n^-1 mod 2^32
+__device__ __forceinline__ uint32_t ord32(int i) { return (uint32_t)(ORD[i >> 1] >> (32 * (i & 1))); }
+
+// The response r = v - sk c mod n.  v, c: scalars below n; skr = sk 2^256 mod n, so that one Montgomery
+// multiplication (8 x 32-bit CIOS, modulus n) by c gives sk c mod n; then a subtraction with conditional add-back.
+// All limbs little-endian; every array index is a literal after unrolling.
+__device__ __forceinline__ void schnorr_response(const uint32_t (&v)[8], const uint32_t (&skr)[8],
+                                                 const uint32_t (&c)[8], uint32_t (&r)[8]) {
+  uint32_t t[10];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) t[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    u64 cur, carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      cur = (u64)skr[j] * c[i] + t[j] + carry;
+      t[j] = (uint32_t)cur;
+      carry = cur >> 32;
+    }
+    cur = (u64)t[8] + carry;
+    t[8] = (uint32_t)cur;
+    t[9] = (uint32_t)(cur >> 32);
+    const uint32_t m = t[0] * ORD_N0INV;
+    cur = (u64)m * ord32(0) + t[0];
+    carry = cur >> 32;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+      cur = (u64)m * ord32(j) + t[j] + carry;
+      t[j - 1] = (uint32_t)cur;
+      carry = cur >> 32;
+    }
+    cur = (u64)t[8] + carry;
+    t[7] = (uint32_t)cur;
+    t[8] = t[9] + (uint32_t)(cur >> 32);
+  }
+  // t < 2 n: x = t - n when t >= n
+  uint32_t x[8];
+  u64 borrow = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const u64 d = (u64)t[j] - ord32(j) - borrow;
+    x[j] = (uint32_t)d;
+    borrow = (d >> 32) & 1;
+  }
+  const bool keep = t[8] == 0 && borrow != 0;   // t < n
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = keep ? t[j] : x[j];
+  // r = v - x, + n when it borrows
+  borrow = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const u64 d = (u64)v[j] - x[j] - borrow;
+    r[j] = (uint32_t)d;
+    borrow = (d >> 32) & 1;
+  }
+  const uint32_t back = borrow ? 0xffffffffu : 0u;
+  u64 carry = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const u64 s = (u64)r[j] + (ord32(j) & back) + carry;
+    r[j] = (uint32_t)s;
+    carry = s >> 32;
+  }
+}
+
+// four little-endian 64-bit limbs <-> eight 32-bit ones
+__device__ __forceinline__ void limbs32(uint32_t (&k)[8], const u64 (&v)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    k[2 * j] = (uint32_t)v[j];
+    k[2 * j + 1] = (uint32_t)(v[j] >> 32);
+  }
+}
+// a scalar's 32 big-endian bytes as four little-endian 64-bit words of the byte string
+__device__ __forceinline__ void scalar_be_words(u64 (&w)[4], const uint32_t (&k)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = __builtin_bswap64(((u64)k[7 - 2 * j] << 32) | k[6 - 2 * j]);
+}
+
+// 36 bytes of nonce entropy = the signer's 32-byte base (4-byte aligned) and the little-endian nonce id, as the
+// key block's words
+__device__ __forceinline__ void ld_entropy(u64 (&m)[8], const uint32_t* base, uint32_t id) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m[i] = (u64)base[2 * i] | ((u64)base[2 * i + 1] << 32);
+  m[4] = id;
+  m[5] = m[6] = m[7] = 0;
 }
 
 }  // namespace
@@ -391,6 +509,130 @@ extern "C" __global__ void __launch_bounds__(64) k_schnorr_point(const uint8_t* 
   st_words64(reinterpret_cast<uint32_t*>(out + (long long)t * 64), m);
 }
 
+// The signer (run_sign_job, schnorr_sign): item t signs message msg_idx[t] with local key key_idx[t] and nonce id
+// nonce_id[t].  messages: uint8 [nmsg][64]; keys: [nkeys][8] limbs of sk 2^256 mod n; bases: uint8 [nkeys][32] the
+// nonce bases; table: base 0 of a (B0 = 8, NW = 33) table, G; sigs: uint8 [n][64] (c || r, zeros unless status 0);
+// status: int [n], 0 signed | 3 a XOF found no candidate in DRAWS (the host signs) | 4 an index out of range;
+// counter (may be null): incremented once per item whose status is not 0.
+// Grid as the verifier's.  Every lane of an item draws the nonce v itself (the wave runs the XOF once either way);
+// lane q sums windows 0..8 (q = 0) or 8 q + 1 .. 8 q + 8 of v G; lane 0 adds, marshals, hashes, responds, stores.
+extern "C" __global__ void __launch_bounds__(64) k_schnorr_sign(const uint8_t* __restrict__ messages,
+                                                               const int* __restrict__ msg_idx,
+                                                               const int* __restrict__ key_idx,
+                                                               const uint32_t* __restrict__ nonce_id,
+                                                               const uint32_t* __restrict__ keys,
+                                                               const uint8_t* __restrict__ bases,
+                                                               const uint32_t* __restrict__ table, int nkeys,
+                                                               int nmsg, int n, uint8_t* __restrict__ sigs,
+                                                               int* __restrict__ status, int* counter) {
+  __shared__ __align__(16) uint32_t s_part[4][SP][24];
+  __shared__ uint32_t s_v[SP][8];
+  const int p = threadIdx.x & (SP - 1), q = threadIdx.x >> 4;
+  const int t = blockIdx.x * SP + p;
+  const bool valid = t < n;
+  int mi = -1, ki = -1;
+  uint32_t id = 0;
+  if (valid) {
+    mi = msg_idx[t];
+    ki = key_idx[t];
+    id = nonce_id[t];
+  }
+  const bool in_range = valid && mi >= 0 && mi < nmsg && ki >= 0 && ki < nkeys;
+  u64 ent[8], v64[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ent[i] = 0;
+  if (in_range) ld_entropy(ent, reinterpret_cast<const uint32_t*>(bases + (long long)ki * 32), id);
+  const int vdraws = schnorr_xof(XOF_KEY36, ent, false, ent, v64);   // (an item out of range draws from zeros, unused)
+  const bool act = in_range && vdraws != 0;
+  uint32_t v[8];
+  limbs32(v, v64);
+  if (q == 0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s_v[p][i] = act ? v[i] : 0u;
+  }
+  __syncthreads();
+  jac acc = jac_inf();
+  if (act) acc = window_sum(&s_v[p][0], table, q == 0 ? 0 : 8 * q + 1, q == 0 ? 9 : 8);
+  st_jac(&s_part[q][p][0], acc);
+  __syncthreads();
+  // ---------------- the last barrier is behind us: one lane per item finishes
+  if (!(valid && q == 0)) return;
+  int st = !in_range ? 4 : vdraws == 0 ? 3 : 0;
+  u64 out[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (st == 0) {
+    u64 key[8], msg[8], ch[4];
+    marshal_sum(p, s_part, key);
+    ld_words64(msg, reinterpret_cast<const uint32_t*>(messages + (long long)mi * 64));
+    if (schnorr_challenge(key, msg, ch) == 0) {
+      st = 3;
+    } else {
+      uint32_t c[8], skr[8], r[8];
+      limbs32(c, ch);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) skr[i] = keys[(long long)ki * 8 + i];
+      schnorr_response(v, skr, c, r);
+      u64 cw[4], rw[4];
+      scalar_be_words(cw, c);
+      scalar_be_words(rw, r);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        out[j] = cw[j];
+        out[4 + j] = rw[j];
+      }
+    }
+  }
+  st_words64(reinterpret_cast<uint32_t*>(sigs + (long long)t * 64), out);
+  status[t] = st;
+  if (st != 0 && counter != nullptr) atomicAdd(counter, 1);
+}
+
+// Test entry point: the nonce alone.  entropy: uint8 [n][36] (a signer's base || le32(nonce id)); scalar: uint8
+// [n][32] the nonce, big-endian (zeros at the draw cap); draws: int [n] the candidates drawn, 0 at the cap.
+extern "C" __global__ void __launch_bounds__(64) k_schnorr_nonce(const uint8_t* __restrict__ entropy, int n,
+                                                                uint8_t* __restrict__ scalar,
+                                                                int* __restrict__ draws) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t* e = reinterpret_cast<const uint32_t*>(entropy + (long long)t * 36);
+  u64 ent[8], v[4] = {0, 0, 0, 0};
+  ld_entropy(ent, e, e[8]);
+  const int used = schnorr_xof(XOF_KEY36, ent, false, ent, v);
+  uint32_t* o = reinterpret_cast<uint32_t*>(scalar + (long long)t * 32);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {   // big-endian: limb 3 first
+    const u64 be = used ? __builtin_bswap64(v[3 - j]) : 0ull;
+    o[2 * j] = (uint32_t)be;
+    o[2 * j + 1] = (uint32_t)(be >> 32);
+  }
+  draws[t] = used;
+}
+
+// Test entry point: the response alone.  vs, cs: uint8 [n][32] big-endian scalars below n; skr: [n][8] limbs of
+// sk 2^256 mod n; out: uint8 [n][32] v - sk c mod n, big-endian.
+extern "C" __global__ void __launch_bounds__(64) k_schnorr_response(const uint8_t* __restrict__ vs,
+                                                                   const uint32_t* __restrict__ skr,
+                                                                   const uint8_t* __restrict__ cs, int n,
+                                                                   uint8_t* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  uint32_t v[8], c[8], k[8], r[8];
+  ld_scalar_be(v, reinterpret_cast<const uint32_t*>(vs + (long long)t * 32));
+  ld_scalar_be(c, reinterpret_cast<const uint32_t*>(cs + (long long)t * 32));
+#pragma unroll
+  for (int i = 0; i < 8; ++i) k[i] = skr[(long long)t * 8 + i];
+  schnorr_response(v, k, c, r);
+  u64 w[4];
+  scalar_be_words(w, r);
+  uint32_t* o = reinterpret_cast<uint32_t*>(out + (long long)t * 32);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    o[2 * j] = (uint32_t)w[j];
+    o[2 * j + 1] = (uint32_t)(w[j] >> 32);
+  }
+}
+
 namespace {
 inline bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 }  // namespace
@@ -417,6 +659,41 @@ extern "C" int bsc_schnorr_challenge(const uint8_t* tm, const uint8_t* messages,
   if (misaligned4(tm) || misaligned4(messages) || misaligned4(scalar)) return -1;
   hipLaunchKernelGGL(k_schnorr_challenge, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, tm, messages, n,
                      scalar, draws);
+  return (int)hipGetLastError();
+}
+
+// The contract of bsc_schnorr_verify: -1 and no launch for n < 0, nkeys < 1, nmsg < 1, a null required pointer or a
+// byte buffer that is not 4-byte aligned; 0 and no launch for n == 0.  counter may be null.
+extern "C" int bsc_schnorr_sign(const uint8_t* messages, const int* msg_idx, const int* key_idx,
+                                const uint32_t* nonce_id, const uint32_t* keys, const uint8_t* bases,
+                                const uint32_t* table, int nkeys, int nmsg, int n, uint8_t* sigs, int* status,
+                                int* counter, void* stream) {
+  if (n < 0 || nkeys < 1 || nmsg < 1) return -1;
+  if (n == 0) return 0;
+  if (!messages || !msg_idx || !key_idx || !nonce_id || !keys || !bases || !table || !sigs || !status) return -1;
+  if (misaligned4(messages) || misaligned4(bases) || misaligned4(sigs)) return -1;
+  hipLaunchKernelGGL(k_schnorr_sign, dim3((n + SP - 1) / SP), dim3(64), 0, (hipStream_t)stream, messages, msg_idx,
+                     key_idx, nonce_id, keys, bases, table, nkeys, nmsg, n, sigs, status, counter);
+  return (int)hipGetLastError();
+}
+
+extern "C" int bsc_schnorr_nonce(const uint8_t* entropy, int n, uint8_t* scalar, int* draws, void* stream) {
+  if (n < 0) return -1;
+  if (n == 0) return 0;
+  if (!entropy || !scalar || !draws) return -1;
+  if (misaligned4(entropy) || misaligned4(scalar)) return -1;
+  hipLaunchKernelGGL(k_schnorr_nonce, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, entropy, n, scalar,
+                     draws);
+  return (int)hipGetLastError();
+}
+
+extern "C" int bsc_schnorr_response(const uint8_t* vs, const uint32_t* skr, const uint8_t* cs, int n, uint8_t* out,
+                                    void* stream) {
+  if (n < 0) return -1;
+  if (n == 0) return 0;
+  if (!vs || !skr || !cs || !out) return -1;
+  if (misaligned4(vs) || misaligned4(cs) || misaligned4(out)) return -1;
+  hipLaunchKernelGGL(k_schnorr_response, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, vs, skr, cs, n, out);
   return (int)hipGetLastError();
 }
 

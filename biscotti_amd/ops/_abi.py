@@ -45,6 +45,9 @@ SIGNATURES = {
     "bsc_schnorr_verify": [P, P, P, P, P, I, I, I, P, P, P],
     "bsc_schnorr_challenge": [P, P, I, P, P, P],
     "bsc_schnorr_point": [P, P, P, P, I, I, P, P],
+    "bsc_schnorr_sign": [P, P, P, P, P, P, P, I, I, I, P, P, P, P],
+    "bsc_schnorr_nonce": [P, I, P, P, P],
+    "bsc_schnorr_response": [P, P, P, I, P, P],
     # kzg.hip
     "bsc_kzg_blocks": [I, I],
     "bsc_kzg_rlc": [P, P, P, P, I, I, I, P, I, I, U64, P, P, P],

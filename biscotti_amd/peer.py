@@ -37,7 +37,7 @@ import sys
 from .protocol.config import add_framework_flags, add_reference_flags, config_from_args
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="biscotti_amd.peer", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     add_reference_flags(ap)
@@ -51,6 +51,14 @@ def main(argv=None) -> int:
     ap.add_argument("--rpc-flood", default="", help="comma list of HOST:PORT peers that receive every block")
     ap.add_argument("--rpc-peer", action="store_true",
                     help="run as one peer over net/rpc (the reference's deployment; needs -i and -t)")
+    ap.add_argument("--device-sign", action="store_true",
+                    help="the verifiers' Schnorr signatures from k_schnorr_sign (kernels/schnorr.hip) instead of the "
+                         "host's signing pool: the same bytes (engine.sign_device; a CPU engine signs on the host)")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     ns = ap.parse_args(argv)
     cfg = config_from_args(ns)
     if cfg.num_nodes <= 0 or not cfg.dataset:
@@ -75,6 +83,7 @@ def main(argv=None) -> int:
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
     eng = BiscottiEngine(cfg, comm)
+    eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
         from .parallel import netrpc

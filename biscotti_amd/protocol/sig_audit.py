@@ -13,6 +13,9 @@ what it keeps; engine.sig_audit_keep overrides the bound).  On the CPU, or for s
 decides.  drain() sets stats["sig_audit_checked"] and stats["sig_audit_failures"] and logs the first failure once
 per run with iteration, verifier and worker.  A failure never changes the chain; no collective is added.  Test seam:
 engine.sig_audit_tamper(sig_np, iteration), applied to the audit's own copy of the matrix.
+
+The device signer (engine.sign_device, `peer --device-sign`; k_schnorr_sign) lives here too: it shares the verifier's
+streams and, where the run has a verifier, its table of G.  With the switch off nothing of it is built or launched.
 """
 from __future__ import annotations
 
@@ -24,7 +27,28 @@ from ..utils import streams as S
 SIG_AUDIT_KEEP = 256   # batches kept unread at most
 
 
+class _DeviceSignJob:
+    """What _join_signatures reads of a device batch: the host SignJob's result_array()."""
+
+    def __init__(self, wait, stats: dict):
+        self._wait, self._stats = wait, stats
+
+    def done(self) -> bool:
+        return bool(self._wait.ready())
+
+    def result_array(self) -> np.ndarray:
+        sigs, status, replaced = self._wait()
+        if status.any():   # (the engine's indices are in range by construction: status 4 is a bug)
+            raise RuntimeError(f"device signer: statuses {sorted(set(status[status != 0].tolist()))} left unsigned")
+        self._stats["sign_device"] = self._stats.get("sign_device", 0) + int(status.size) - replaced
+        self._stats["sign_device_host"] = self._stats.get("sign_device_host", 0) + replaced
+        return sigs
+
+
 class SigAuditMixin:
+    _sign_on = False                    # engine.sign_device
+    _sign_dev = None                    # ops.schnorr.SchnorrSigner, lazily
+
     def _sig_audit_init(self, cfg) -> None:
         self._sig_dev = None            # ops.schnorr.SchnorrVerifier, lazily
         self._sig_stream = None         # the quorum check's stream (high priority: the round waits for it)
@@ -46,10 +70,7 @@ class SigAuditMixin:
             if sv is not None:
                 torch.cuda.synchronize(self.dev)
                 sv.release()
-            if self._sig_stream is None:
-                lo, hi = torch.cuda.Stream.priority_range()
-                self._sig_stream = torch.cuda.Stream(device=self.dev, priority=hi)
-                self._sig_audit_stream = torch.cuda.Stream(device=self.dev, priority=lo)
+            self._sig_streams()
             with S.use(self._sig_stream):
                 sv = self._sig_dev = SchnorrVerifier(pks, self.dev)
             torch.cuda.synchronize(self.dev)   # the tables are visible to every stream
@@ -60,7 +81,58 @@ class SigAuditMixin:
         sv, self._sig_dev = self._sig_dev, None
         if sv is not None:
             sv.release()
+        sg, self._sign_dev = self._sign_dev, None
+        if sg is not None:
+            sg.release()
         self._sig_stream = self._sig_audit_stream = None
+
+    # ------------------------------------------------------------------ engine.sign_device (--device-sign)
+    @property
+    def sign_device(self) -> bool:
+        """The verifiers' signatures come from k_schnorr_sign (ops.schnorr.SchnorrSigner) instead of the host's
+        SignJob: the same bytes.  Off by default; on a CPU engine the switch is accepted and the host signs.
+        Stats (present once the switch has been set): sign_device (signatures the kernel produced),
+        sign_device_host (status-3 items the host signed), sign_table_bytes (0 for a borrowed table)."""
+        return self._sign_on
+
+    @sign_device.setter
+    def sign_device(self, on) -> None:
+        self._sign_on = bool(on)
+        if self._sign_on:
+            for k in ("sign_device", "sign_device_host", "sign_table_bytes"):
+                self.stats.setdefault(k, 0)
+
+    def _sig_streams(self) -> None:
+        if self._sig_stream is None:
+            lo, hi = torch.cuda.Stream.priority_range()
+            self._sig_stream = torch.cuda.Stream(device=self.dev, priority=hi)
+            self._sig_audit_stream = torch.cuda.Stream(device=self.dev, priority=lo)
+
+    def _sig_signer(self):
+        """The engine's device signer, created at the first signed batch; it borrows the verifier's table of G
+        where this run has a verifier (--verify-signatures, --sig-audit)."""
+        sg = self._sign_dev
+        if sg is None:
+            from ..ops.schnorr import SchnorrSigner
+
+            cfg = self.cfg
+            wanted = cfg.sig_audit or (cfg.verify_signatures and cfg.verification and cfg.secure_agg)
+            sv = self._sig_verifier() if (self._sig_dev is not None or wanted) else None
+            self._sig_streams()
+            with S.use(self._sig_stream):
+                sg = self._sign_dev = SchnorrSigner(self.dev, table=sv)
+            torch.cuda.synchronize(self.dev)   # the table is visible to every stream
+            self.stats["sign_table_bytes"] = sg.table_bytes()
+        return sg
+
+    def _sign_on_device(self, msgs: np.ndarray, msg_idx, key_of, nonce_ids, sks: list, bases: list, waited: bool):
+        """Launch one batch of verifier signatures (verify.py _prep_sign) and return its job: result_array() waits
+        for the read-back and lets the host sign what the kernel left undecided.  waited: the round reads this
+        batch before its block (the high-priority stream); a deferred batch goes on the low-priority one."""
+        sg = self._sig_signer()
+        with S.use(self._sig_stream if waited else self._sig_audit_stream):
+            wait = sg.sign_resolved(msgs, msg_idx, key_of, nonce_ids, sks, bases)
+        return _DeviceSignJob(wait, self.stats)
 
     # ------------------------------------------------------------------ --sig-audit
     def _sig_audit_host(self, it: int, items: list, msgs, pks: list, sigs, which) -> None:

@@ -530,7 +530,22 @@ class VerifyMixin:
                         bases = [_seed_bytes(cfg.seed, f"nonce-{i}", v) for v, i in nonce_keys]
                         sign["sl"] = (vidx[kk], jj)
                         jac = getattr(commit_of, "jac", None)
-                        if jac is not None and commit_of._table is None:
+                        if self.sign_device and self.gpu:
+                            # k_schnorr_sign: one launch and one read-back, no host thread and so no after_vrf gate;
+                            # each signed commitment is marshalled once (several verifiers sign the same worker's)
+                            uw, inv = np.unique(ws, return_inverse=True)
+                            if jac is not None and commit_of._table is None:
+                                S.host_wait(jac[1])
+                                jrows = jac[0].numpy().view(np.uint32)
+                                msgs = R.g1_marshal_jac_batch(np.ascontiguousarray(jrows[rmap[uw]]))
+                            else:
+                                msgs = np.ascontiguousarray(commit_of.table[rmap[uw]])
+                            msgs = np.asarray(msgs, np.uint8).reshape(-1, 64)
+                            sign["job"] = self._sign_on_device(msgs, inv, kk, ws, sks, bases, waited=not defer_sign)
+                            if cfg.sig_audit:
+                                sign["msgs"] = np.ascontiguousarray(msgs[inv])
+                                sign["pks"] = [self.pk[local_vs[k]] for k in kk.tolist()]
+                        elif jac is not None and commit_of._table is None:
                             # the commitments are still the pre-step's Jacobian rows: the job marshals the signed
                             # ones on its own thread (the round's thread skips the table's ~30 us marshal)
                             S.host_wait(jac[1])

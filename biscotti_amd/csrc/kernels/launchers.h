@@ -37,6 +37,10 @@ int bsc_softmax_step(const float* X, const int* y, const long long* off, const i
                      const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed, int iteration,
                      float max_norm, double qscale, float* delta, long long* qdelta, float* loss, int lo, int* ones,
                      int nones, void* stream);
+int bsc_margin_step(const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,
+                    const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed, int iteration,
+                    float max_norm, double qscale, float* delta, long long* qdelta, float* loss, int lo, int* ones,
+                    int nones, void* stream);
 int bsc_gram_stacked_range(const float* X, int U1, const float* X2, int U2, long long stride2, int D, int kchunk,
                            int p0, int p1, double* part, double* gram, unsigned int* count, const double* nn,
                            void* stream);

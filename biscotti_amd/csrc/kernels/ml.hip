@@ -2,7 +2,8 @@
 //   K1  batched softmax-regression local step: minibatch draw, (x-0.5)/0.5 transform, logits
 //       (f32 MFMA), softmax + CE, backward dW (f32 MFMA) / db, clip_grad_norm(100), negate,
 //       fixed-point quantisation -- one workgroup per virtual peer
-//       (ML/Pytorch/client.py:38-65, client_obj.py:73-77, DistSys/kyber.go:698-710)
+//       (ML/Pytorch/client.py:38-65, client_obj.py:73-77, DistSys/kyber.go:698-710); the same body under the
+//       multi-class margin loss is the SVM task's step (k_margin_step; svm_model.py, client.py:28)
 //   K3  batched logistic-regression step with DP noise at source (ML/code/logistic_model.py:92-140)
 //   K4  counter-based Gaussian DP noise, averaged over each worker's noisers, added to the delta
 //       (client_obj.py:42-67,97-98; DistSys/main.go:1592-1660,1530-1537)
@@ -67,7 +68,45 @@ __device__ __forceinline__ long long quantize(float v, double scale) {
 constexpr int SM_MAXK = 1024;
 constexpr int SM_THREADS = 256;
 
-extern "C" __global__ void __launch_bounds__(SM_THREADS) k_softmax_step(
+namespace {
+// Step 4 of the local step, one struct per loss of the linear scorer: from one minibatch row's logits lg[0, D_OUT)
+// and its label, the row of G = d(mean loss) / d(logits) (already divided by Bq) into g[0, D_OUT); returns the
+// row's loss.  Everything around it (draw, transform, logits, dW / db, clip, quantisation) is linear_step_body.
+struct CrossEntropyLoss {  // softmax + cross-entropy (nn.CrossEntropyLoss, client.py:29)
+  static __device__ __forceinline__ float row(const float* lg, int D_OUT, int lab, int Bq, float* g) {
+    float mx = -INFINITY;
+    for (int c = 0; c < D_OUT; ++c) mx = fmaxf(mx, lg[c]);
+    float se = 0.f;
+    for (int c = 0; c < D_OUT; ++c) se += expf(lg[c] - mx);
+    for (int c = 0; c < D_OUT; ++c) g[c] = (expf(lg[c] - mx) / se - (c == lab ? 1.f : 0.f)) / (float)Bq;
+    return (mx + logf(se)) - lg[lab];
+  }
+};
+// multi-class margin loss with the row's single target (SVMModel under nn.MultiLabelMarginLoss with the target
+// [y, -1, ...], client.py:28 == F.multi_margin_loss(p = 1, margin = 1)): sum_{c != y} max(0, 1 - x_y + x_c) / C.
+// Active where z > 0 strictly, like torch: a hinge at exactly 0 gives no gradient.
+struct MarginLoss {
+  static __device__ __forceinline__ float row(const float* lg, int D_OUT, int lab, int Bq, float* g) {
+    const float xy = lg[lab];
+    const float w = 1.f / ((float)D_OUT * (float)Bq);
+    float l = 0.f;
+    int act = 0;
+    for (int c = 0; c < D_OUT; ++c) {
+      const float z = 1.f - xy + lg[c];
+      const bool on = c != lab && z > 0.f;
+      g[c] = on ? w : 0.f;
+      if (on) {
+        l += z;
+        ++act;
+      }
+    }
+    g[lab] = -(float)act * w;
+    return l / (float)D_OUT;
+  }
+};
+
+template <class Loss>
+__device__ __forceinline__ void linear_step_body(
     const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
     int D_OUT, int B, int P, unsigned long long seed, int iteration, float max_norm, double qscale, float* delta,
     long long* qdelta, float* loss, int lo, int* ones, int nones) {
@@ -80,7 +119,7 @@ extern "C" __global__ void __launch_bounds__(SM_THREADS) k_softmax_step(
     for (int i = threadIdx.x; i < nones; i += blockDim.x) ones[i] = 1;
   __shared__ float xs[16 * SM_MAXK];  // minibatch rows, transformed; rows >= B are zero
   __shared__ float red[4][16][16];    // per-wave partial logits
-  __shared__ float G[16][16];         // (softmax - onehot) / B
+  __shared__ float G[16][16];         // d(mean loss) / d(logits): (softmax - onehot) / B, or the margin's +-1 / (C B)
   __shared__ int bidx[16];
   __shared__ float nrm[SM_THREADS / 64];
   __shared__ float scale_sh;
@@ -145,22 +184,16 @@ extern "C" __global__ void __launch_bounds__(SM_THREADS) k_softmax_step(
     for (int r = 0; r < 4; ++r) red[wid][(lane >> 4) * 4 + r][lane & 15] = acc[r];
   }
   __syncthreads();
-  // 4. softmax + cross-entropy on rows s < Bq (one thread per row)
+  // 4. the loss and its gradient with respect to the logits on rows s < Bq (one thread per row)
   if (tid < 16) {
     const int s = tid;
     if (s < Bq) {
       float lg[16];
-      float mx = -INFINITY;
-      for (int c = 0; c < D_OUT; ++c) {
+      for (int c = 0; c < D_OUT; ++c)
         lg[c] = red[0][s][c] + red[1][s][c] + red[2][s][c] + red[3][s][c] + (float)W[D_OUT * D_IN + c];
-        mx = fmaxf(mx, lg[c]);
-      }
-      float se = 0.f;
-      for (int c = 0; c < D_OUT; ++c) se += expf(lg[c] - mx);
-      const int lab = y[offp + bidx[s]];
-      for (int c = 0; c < D_OUT; ++c) G[s][c] = (expf(lg[c] - mx) / se - (c == lab ? 1.f : 0.f)) / (float)Bq;
+      const float l = Loss::row(lg, D_OUT, y[offp + bidx[s]], Bq, G[s]);
       for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
-      red[0][s][0] = (mx + logf(se)) - lg[lab];  // per-row CE (red no longer needed)
+      red[0][s][0] = l;  // per-row loss (red no longer needed)
     } else {
       for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
     }
@@ -230,6 +263,24 @@ extern "C" __global__ void __launch_bounds__(SM_THREADS) k_softmax_step(
     dst[i] = v;
     qd[i] = quantize(v, qscale);
   }
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(SM_THREADS) k_softmax_step(
+    const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
+    int D_OUT, int B, int P, unsigned long long seed, int iteration, float max_norm, double qscale, float* delta,
+    long long* qdelta, float* loss, int lo, int* ones, int nones) {
+  linear_step_body<CrossEntropyLoss>(X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale,
+                                     delta, qdelta, loss, lo, ones, nones);
+}
+
+// K1, margin form: the same step of the same linear scorer under the multi-class margin loss (the SVM task)
+extern "C" __global__ void __launch_bounds__(SM_THREADS) k_margin_step(
+    const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
+    int D_OUT, int B, int P, unsigned long long seed, int iteration, float max_norm, double qscale, float* delta,
+    long long* qdelta, float* loss, int lo, int* ones, int nones) {
+  linear_step_body<MarginLoss>(X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, delta,
+                               qdelta, loss, lo, ones, nones);
 }
 
 // =====================================================================================
@@ -1540,6 +1591,18 @@ extern "C" int bsc_softmax_step(const float* X, const int* y, const long long* o
   if (D_IN <= 0 || D_OUT > 16 || B > 16) return -1;
   if (P <= 0) return 0;
   hipLaunchKernelGGL(k_softmax_step, dim3(P), dim3(SM_THREADS), 0, (hipStream_t)stream, X, y, off, ntrain, pid, W, D_IN,
+                     D_OUT, B, P, seed, iteration, max_norm, qscale, delta, qdelta, loss, lo, ones, nones);
+  return (int)hipGetLastError();
+}
+
+// the margin form: bsc_softmax_step's arguments, limits and geometry
+extern "C" int bsc_margin_step(const float* X, const int* y, const long long* off, const int* ntrain,
+                               const int* pid, const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed,
+                               int iteration, float max_norm, double qscale, float* delta, long long* qdelta,
+                               float* loss, int lo, int* ones, int nones, void* stream) {
+  if (D_IN <= 0 || D_OUT > 16 || B > 16) return -1;
+  if (P <= 0) return 0;
+  hipLaunchKernelGGL(k_margin_step, dim3(P), dim3(SM_THREADS), 0, (hipStream_t)stream, X, y, off, ntrain, pid, W, D_IN,
                      D_OUT, B, P, seed, iteration, max_norm, qscale, delta, qdelta, loss, lo, ones, nones);
   return (int)hipGetLastError();
 }

@@ -51,6 +51,7 @@ struct PreSlot {  // one slot of the pre-step's output ring
 };
 struct TaskCfg {  // the softmax task's resident data and the pre-step's constants
   int bound = 0;
+  int loss = 0;   // the local step's loss: 0 cross-entropy (k_softmax_step), 1 margin (k_margin_step)
   hipStream_t gram;
   const float* X;
   const int *y, *ntrain, *pid, *rows_arange;
@@ -498,7 +499,17 @@ extern "C" int bsc_round_bind_task(void* ctx, void* gram_stream, const float* X,
   t.nn_tab = nullptr;
   t.kchunk = kchunk;
   t.counters = counters;
+  t.loss = 0;
   t.bound = 1;
+  return 0;
+}
+
+// The bound task's loss (0: cross-entropy, the default of every bind; 1: margin, the SVM task): which local-step
+// kernel the pre-step queues.
+extern "C" int bsc_round_task_loss(void* ctx, int loss) {
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || !c->task.bound || loss < 0 || loss > 1) return -1;
+  c->task.loss = loss;
   return 0;
 }
 
@@ -582,8 +593,9 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
   RC_CHECK(hipEventRecord(c->ev_pre, c->main));
   RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
   if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
-  RC_CHECK(bsc_softmax_step(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.max_norm,
-                            t.qs, p.delta, p.qdelta, p.loss, t.lo, ones, c->spec_cap, gs));
+  RC_CHECK((t.loss == 1 ? bsc_margin_step : bsc_softmax_step)(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B,
+                                                              t.P, t.seed, it, t.max_norm, t.qs, p.delta, p.qdelta,
+                                                              p.loss, t.lo, ones, c->spec_cap, gs));
   RC_CHECK(hipEventRecord(p.ev_step, gs));
   RC_CHECK(hipStreamWaitEvent(c->bg, p.ev_step, 0));
   RC_CHECK(bsc_shares_msm(p.qdelta, c->d, t.rows_arange, t.P, c->tbl_pk, t.tbl_wb, c->poly, c->T, c->b0, c->nw, 1,

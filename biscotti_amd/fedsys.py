@@ -14,13 +14,21 @@ import sys
 from .protocol.config import add_framework_flags, add_reference_flags, config_from_args
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="biscotti_amd.fedsys", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     add_reference_flags(ap)
     add_framework_flags(ap)
     ap.set_defaults(perc_samples=35, epsilon=5.0)
     ap.add_argument("--rounds", type=int, default=None)
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm"],
+                    help="softmax regression, or svm: the same linear scorer under the multi-class margin loss "
+                         "(mnist and lfw)")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     ns = ap.parse_args(argv)
     cfg = config_from_args(ns)
     if cfg.num_nodes <= 1 or not cfg.dataset:
@@ -39,7 +47,7 @@ def main(argv=None) -> int:
     from .protocol.fedsys import FedSysEngine
 
     comm = Comm.init(device=cfg.device)
-    eng = FedSysEngine(cfg, comm)
+    eng = FedSysEngine(cfg, comm, model=ns.model)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

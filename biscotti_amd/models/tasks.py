@@ -1,6 +1,7 @@
 """Batched learning tasks: all virtual peers hosted by one rank as device tensors.
 
-SoftmaxTask  -- MNIST softmax regression (the Biscotti path; ML/Pytorch/client_obj.py + client.py)
+SoftmaxTask  -- MNIST softmax regression (the Biscotti path; ML/Pytorch/client_obj.py + client.py); with
+                loss="margin" the same scorer as the reference's SVM (svm_model.py, the margin criterion)
 LogisticTask -- creditcard logistic regression (ML/code/logistic_model.py), DP noise at source
 
 ``step(W, iteration)`` runs the local update of every *listed* local peer in one fused kernel and
@@ -24,7 +25,12 @@ class SoftmaxTask:
 
     def __init__(self, peers: range, num_peers: int, device, seed: int, poisoned: set[int] | None = None,
                  batch_size: int = 10, data_dir: str | None = None, federation: D.MnistFederation | None = None,
-                 dims: tuple | None = None):
+                 dims: tuple | None = None, loss: str = "ce"):
+        if loss not in ("ce", "margin"):
+            raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
+        # "margin": the same linear scorer trained as SVMModel (svm_model.py under nn.MultiLabelMarginLoss with
+        # the single target, client.py:28); evaluation, train_error and roni_rows are argmax-based: the same
+        self.loss = loss
         if dims is not None:
             self.d_in, self.d_out = dims
         fed = federation or D.mnist_federation(num_peers, seed=seed, data_dir=data_dir)
@@ -79,8 +85,9 @@ class SoftmaxTask:
             pid = h2d(peers, torch.int32, self.device)
             if len(self._sel_cache) < 64:
                 self._sel_cache[key] = pid
-        delta, qdelta, loss = K.softmax_step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
-                                             self.batch, self.seed, iteration, 100.0, 1e4, lo=self.peers[0])
+        step = K.margin_step if self.loss == "margin" else K.softmax_step
+        delta, qdelta, loss = step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out, self.batch,
+                                   self.seed, iteration, 100.0, 1e4, lo=self.peers[0])
         self.last_loss = loss
         return delta, qdelta
 
@@ -248,18 +255,28 @@ class LogisticTask:
         return result
 
 
-def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, **kw):
+MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
+
+
+def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax", **kw):
+    """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
+    loss="margin"); creditcard has its logistic model only."""
+    if model not in MODELS:
+        raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
+    if model == "svm" and dataset == "creditcard":
+        raise ValueError("model 'svm' needs a multi-class dataset (mnist, lfw): creditcard trains its logistic model")
+    loss = "margin" if model == "svm" else "ce"
     if dataset == "mnist":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)
-        return SoftmaxTask(peers, num_peers, device, seed, **kw)
+        return SoftmaxTask(peers, num_peers, device, seed, loss=loss, **kw)
     if dataset == "lfw":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)
         kw.pop("data_dir", None)
         _, d_in, d_out = D.dataset_dims("lfw")
         return SoftmaxTask(peers, num_peers, device, seed, federation=D.lfw_federation(num_peers, seed=seed),
-                           dims=(d_in, d_out), **kw)
+                           dims=(d_in, d_out), loss=loss, **kw)
     if dataset == "creditcard":
         kw.pop("data_dir", None)
         kw.pop("federation", None)

@@ -55,6 +55,7 @@ SIGNATURES = {
     "bsc_kzg_rlc_rows": [P, P, P, P, P, I, I, I, I, P, I, U64, P, P, P],
     # ml.hip
     "bsc_softmax_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, P, P, P, I, P, I, P],
+    "bsc_margin_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, P, P, P, I, P, I, P],
     "bsc_logreg_step": [P, P, P, P, P, P, I, I, I, U64, P, D, D, P, D, P, P, P],
     "bsc_dp_noise": [P, I, I, P, I, P, U64, I, P, P],
     "bsc_krum": [P, I, I, I, P, P, P, P, I, I, P],
@@ -87,6 +88,7 @@ SIGNATURES = {
     "bsc_round_bind_outputs": [P, P, I, P, P, P, P, P, P, P],
     "bsc_round_add_layout": [P, P, P, I, P, P, I, P, P, I, U64, U64, P, P],
     "bsc_round_bind_task": [P, P, P, P, P, P, P, I, I, I, I, U64, F, D, I, P, P, P, I, I, P],
+    "bsc_round_task_loss": [P, I],
     "bsc_round_add_pre_slot": [P, P, P, P, P, P, P, P, P, P, P, P, P],
     "bsc_round_prestep_slot": [P, P, I, I],
     "bsc_round_set_nn_table": [P, P],

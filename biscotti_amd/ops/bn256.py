@@ -597,6 +597,8 @@ class NativeSecAgg:
                                          task.seed & (2 ** 64 - 1), 100.0, 1e4, task.peers[0], _ptr(eng.tbl_wb),
                                          _ptr(self.rows_ar), noise_table.data_ptr() if noise_table is not None else None,
                                          U2, kchunk, _ptr(gram_counters)), "round_bind_task")
+        if getattr(task, "loss", "ce") == "margin":   # the pre-step queues k_margin_step (a bind resets it to CE)
+            _check(hip().bsc_round_task_loss(self.ctx, 1), "round_task_loss")
 
         def ev():
             e = torch.cuda.Event()

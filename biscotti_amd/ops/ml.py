@@ -81,15 +81,34 @@ def minibatch_indices(p: int, iteration: int, n: int, B: int, seed: int, tag: in
     return out
 
 
-# ---------------------------------------------------------------------------- K1 softmax step
-def softmax_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm=100.0, qscale=1e4, lo=-1):
-    """Batched local SGD step of SoftmaxModel for every local peer.
+# ---------------------------------------------------------------------------- K1 softmax / margin step
+def _ce_rows(logits, lab):
+    """Cross-entropy: (mean loss, d loss / d logits) of a minibatch's logits [Bq, C]."""
+    g = (torch.softmax(logits, 1) - torch.nn.functional.one_hot(lab, logits.shape[1]).float()) / logits.shape[0]
+    return torch.nn.functional.cross_entropy(logits, lab), g
 
-    X fp32 [Ntot, d_in]; y int32 [Ntot]; off int64 [P]; ntrain int32 [P]; pid int32 [P] global peer
-    ids (key of each peer's minibatch stream); W fp64 [nparam].  lo >= 0: off / ntrain are indexed by
-    local peer id pid - lo (resident arrays over all local peers) instead of by row.
-    Returns (delta fp32 [P, nparam] = -clip(grad), qdelta int64 [P, nparam], loss fp32 [P]).
-    """
+
+def _margin_rows(logits, lab):
+    """Multi-class margin loss with each row's single target (F.multi_margin_loss, p = 1, margin = 1): a hinge
+    z = 1 - x_y + x_c is active where z > 0 strictly; G = 1 / (C Bq) there, -(active count) / (C Bq) at the label."""
+    Bq, C = logits.shape
+    r = torch.arange(Bq)
+    z = 1.0 - logits[r, lab][:, None] + logits
+    on = z > 0
+    on[r, lab] = False
+    w = 1.0 / (C * Bq)
+    g = on.float() * w
+    g[r, lab] = -on.sum(1).float() * w
+    return torch.nn.functional.multi_margin_loss(logits, lab), g
+
+
+_LINEAR_STEPS = {"softmax_step": ("bsc_softmax_step", _ce_rows), "margin_step": ("bsc_margin_step", _margin_rows)}
+
+
+def _linear_step(what, X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo):
+    """The local step of the linear scorer under one loss of _LINEAR_STEPS: its launcher on a GPU, on the CPU the
+    torch fp32 path (the minibatch draw, the transform, the clip and the quantisation are the same for every loss)."""
+    launcher, loss_rows = _LINEAR_STEPS[what]
     P = pid.numel()
     nparam = d_out * d_in + d_out
     dev = X.device
@@ -100,9 +119,9 @@ def softmax_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max
         assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
         assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
         assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
-        _check(hip().bsc_softmax_step(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, d_out, B, P, seed & (2**64 - 1),
-                                      iteration, float(max_norm), float(qscale), _p(delta), _p(qdelta), _p(loss),
-                                      int(lo), None, 0, _stream()), "softmax_step")
+        _check(getattr(hip(), launcher)(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, d_out, B, P,
+                                        seed & (2**64 - 1), iteration, float(max_norm), float(qscale), _p(delta),
+                                        _p(qdelta), _p(loss), int(lo), None, 0, _stream()), what)
         return delta, qdelta, loss
     Wm = W.to(torch.float32)
     Wt, bt = Wm[: d_out * d_in].view(d_out, d_in), Wm[d_out * d_in:]
@@ -117,9 +136,7 @@ def softmax_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max
         rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
         xb = (X[rows] - 0.5) / 0.5
         logits = xb @ Wt.T + bt
-        lab = y[rows].long()
-        lossv = torch.nn.functional.cross_entropy(logits, lab)
-        g = (torch.softmax(logits, 1) - torch.nn.functional.one_hot(lab, d_out).float()) / len(idx)
+        lossv, g = loss_rows(logits, y[rows].long())
         dW, db = g.T @ xb, g.sum(0)
         flat = torch.cat([dW.reshape(-1), db])
         tot = float(torch.linalg.vector_norm(flat))
@@ -131,6 +148,26 @@ def softmax_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max
         qdelta[p] = torch.from_numpy((v.double().numpy() * qscale).astype(np.int64))
         loss[p] = lossv
     return delta, qdelta, loss
+
+
+def softmax_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm=100.0, qscale=1e4, lo=-1):
+    """Batched local SGD step of SoftmaxModel for every local peer.
+
+    X fp32 [Ntot, d_in]; y int32 [Ntot]; off int64 [P]; ntrain int32 [P]; pid int32 [P] global peer
+    ids (key of each peer's minibatch stream); W fp64 [nparam].  lo >= 0: off / ntrain are indexed by
+    local peer id pid - lo (resident arrays over all local peers) instead of by row.
+    Returns (delta fp32 [P, nparam] = -clip(grad), qdelta int64 [P, nparam], loss fp32 [P]).
+    """
+    return _linear_step("softmax_step", X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale,
+                        lo)
+
+
+def margin_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm=100.0, qscale=1e4, lo=-1):
+    """softmax_step for SVMModel: the same linear scorer, minibatch draw, clip and quantisation under the
+    multi-class margin loss mean_s sum_{c != y_s} max(0, 1 - x[s, y_s] + x[s, c]) / C (k_margin_step;
+    nn.MultiLabelMarginLoss with the single target [y, -1, ...], client.py:28).  Arguments and return values are
+    softmax_step's."""
+    return _linear_step("margin_step", X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo)
 
 
 # ---------------------------------------------------------------------------- K3 logistic step

@@ -54,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device-sign", action="store_true",
                     help="the verifiers' Schnorr signatures from k_schnorr_sign (kernels/schnorr.hip) instead of the "
                          "host's signing pool: the same bytes (engine.sign_device; a CPU engine signs on the host)")
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm"],
+                    help="the ledger's model: softmax regression, or svm -- the same linear scorer under the "
+                         "multi-class margin loss (k_margin_step; mnist and lfw).  A chain does not record it: "
+                         "--resume needs the same --model")
     return ap
 
 
@@ -82,7 +86,7 @@ def main(argv=None) -> int:
     from .protocol.engine import BiscottiEngine
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
-    eng = BiscottiEngine(cfg, comm)
+    eng = BiscottiEngine(cfg, comm, model=ns.model)
     eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
@@ -153,7 +157,8 @@ def _rpc_peer_main(cfg, ns) -> int:
     else:
         addrs = [f"127.0.0.1:{8000 + i}" for i in range(cfg.num_nodes)]
     cfg = dataclasses.replace(cfg, device="cpu")
-    peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0)
+    peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0,
+                   model=ns.model)
     try:
         import time
 

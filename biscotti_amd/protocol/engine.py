@@ -78,9 +78,13 @@ class RoundResult:
 
 class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, VrfAuditMixin, SigAuditMixin,
                      FaultsMixin):
-    def __init__(self, cfg: RunConfig, comm: Comm | None = None):
+    def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax"):
         cfg.validate()
         self.cfg = cfg
+        # the ledger's model ("softmax", or "svm": the same scorer under the margin loss; models.make_task).  An
+        # engine switch like sign_device, not a RunConfig field; a chain does not record it: a resumed run must
+        # be given the same one
+        self.model = model
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -120,9 +124,10 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         poisoned = {p for p in self.local if fsm_probe.is_poisoner(p)}
         colluders = {p for p in range(self.N) if fsm_probe.is_colluder(p)}
         self.colluders = colluders
-        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, poisoned=poisoned,
+        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, poisoned=poisoned,
                               batch_size=cfg.batch_size, data_dir=cfg.data_dir, epsilon=cfg.epsilon,
                               colluders=colluders)
+        self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
         # ---- ledger / protocol state
         self.fsm = fsm_probe
         if cfg.peers_file:

@@ -45,11 +45,12 @@ class FedSysResult:
 
 
 class FedSysEngine:
-    def __init__(self, cfg: RunConfig, comm: Comm | None = None):
+    def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax"):
         from ..data import dataset_dims
         from ..models import make_task
 
         self.cfg = cfg
+        self.model = model   # "softmax" or "svm" (models.make_task), as BiscottiEngine's
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -70,9 +71,10 @@ class FedSysEngine:
         self.d = dataset_dims(cfg.dataset)[0]
         probe = self.R.RoundFSM(pc, self.d)
         poisoned = {p for p in self.local if probe.is_poisoner(p, True)}   # FedSys: >= (Q4)
-        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, poisoned=poisoned,
+        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, poisoned=poisoned,
                               batch_size=cfg.batch_size, data_dir=cfg.data_dir, epsilon=cfg.epsilon,
                               colluders=set())
+        self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
         self.W = torch.zeros(self.d, dtype=torch.float64, device=self.dev)
         self.iteration = 0
         self.history: list = []        # BlockData of every model the server broadcast

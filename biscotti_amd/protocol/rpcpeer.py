@@ -38,7 +38,7 @@ from .head import PlanView
 
 class RpcPeer:
     def __init__(self, cfg: RunConfig, peer_id: int, addresses: list[str], host: str = "127.0.0.1",
-                 port: int | None = None, timeout_s: float = 20.0):
+                 port: int | None = None, timeout_s: float = 20.0, *, model: str = "softmax"):
         from ..data import dataset_dims
         from ..models import make_task
         from .engine import _seed_bytes
@@ -51,8 +51,9 @@ class RpcPeer:
         self.fsm = R.RoundFSM(self.pc, self.d)
         self.fsm.addresses = self.addrs
         poisoned = {self.id} if self.fsm.is_poisoner(self.id) else set()
+        self.model = model   # "softmax" or "svm" (models.make_task): every peer of a deployment takes the same one
         self.task = make_task(cfg.dataset, range(self.id, self.id + 1), self.N, torch.device("cpu"), cfg.seed,
-                              poisoned=poisoned, batch_size=cfg.batch_size, epsilon=cfg.epsilon)
+                              model=model, poisoned=poisoned, batch_size=cfg.batch_size, epsilon=cfg.epsilon)
         self.key = R.CommitKey.generate(self.d, 2)   # publicKey.go: s = 2 (every peer derives the same key)
         self.sk, self.pk = R.client_key_from_entropy(_seed_bytes(cfg.seed, "client", self.id))
         self.vrf_seed = _seed_bytes(cfg.seed, "vrf-noise", self.id)

@@ -1,6 +1,7 @@
 """Standalone training sandboxes (ML/Pytorch/ml_main_{mnist,cifar,lfw,credit,diffpriv}.py).
 
     python -m biscotti_amd.sandbox --model softmax --dataset mnist --clients 10 --poisoned 4
+    python -m biscotti_amd.sandbox --model svm --loss margin             # svm_model.py under the margin criterion
     python -m biscotti_amd.sandbox --model mnist_cnn --iters 500
     python -m biscotti_amd.sandbox --model cifar_cnn --dataset cifar
     python -m biscotti_amd.sandbox --model lfw_cnn --dataset lfw
@@ -61,7 +62,10 @@ def _model(name: str, d_in: int, n_classes: int):
 
 
 def run(model="softmax", dataset="mnist", clients=10, poisoned=0, iters=2000, batch=10, lr=1e-3, momentum=0.75,
-        weight_decay=1e-3, eval_every=100, dp_epsilon=0.0, seed=0, device=None, verbose=True) -> dict:
+        weight_decay=1e-3, eval_every=100, dp_epsilon=0.0, seed=0, device=None, verbose=True, loss="ce") -> dict:
+    # loss "margin": the reference's commented-out criterion (nn.MultiLabelMarginLoss, client.py:28) with each
+    # row's single target, == F.multi_margin_loss; --model svm --loss margin is the reference's SVM
+    per_sample = {"ce": F.cross_entropy, "margin": F.multi_margin_loss}[loss]
     dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
     torch.manual_seed(seed)
     Xtr, ytr, Xte, yte, C = _data(dataset, seed)
@@ -87,9 +91,9 @@ def run(model="softmax", dataset="mnist", clients=10, poisoned=0, iters=2000, ba
                 xs.append(Xtr_t[ones[k]]); ys.append(bad_y[k])
         X, Y = torch.cat(xs), torch.cat(ys)
         opt.zero_grad(set_to_none=True)
-        per = F.cross_entropy(net(X), Y, reduction="none").view(clients, batch)
-        loss = per.mean(1).sum()          # sum over clients of each client's mean minibatch loss
-        loss.backward()
+        per = per_sample(net(X), Y, reduction="none").view(clients, batch)
+        total = per.mean(1).sum()         # sum over clients of each client's mean minibatch loss
+        total.backward()
         if sigma > 0:
             for p in net.parameters():    # client_obj.getNoise: per client, averaged over the batch
                 p.grad.add_(torch.randn(p.shape, generator=g, device=dev) * (sigma * math.sqrt(clients) / batch))
@@ -100,10 +104,10 @@ def run(model="softmax", dataset="mnist", clients=10, poisoned=0, iters=2000, ba
                 err = float((pred != yte_t).float().mean())
                 m1 = yte_t == 1
                 att = float((pred[m1] != 1).float().mean()) if bool(m1.any()) else float("nan")
-            hist.append({"iter": it, "loss": float(loss.detach()) / clients, "test_error": err, "attack_rate": att})
+            hist.append({"iter": it, "loss": float(total.detach()) / clients, "test_error": err, "attack_rate": att})
             if verbose:
                 print(f"Average loss is {hist[-1]['loss']:.5f}\nTest error: {err:.5f}\nAttack rate on 1s: {att:.5f}\n")
-    return {"model": model, "dataset": dataset, "final_test_error": hist[-1]["test_error"],
+    return {"model": model, "loss": loss, "dataset": dataset, "final_test_error": hist[-1]["test_error"],
             "final_attack_rate": hist[-1]["attack_rate"], "history": hist}
 
 
@@ -111,6 +115,9 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="biscotti_amd.sandbox", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mnist_cnn", "lfw_cnn", "cifar_cnn"])
+    ap.add_argument("--loss", default="ce", choices=["ce", "margin"],
+                    help="training criterion: cross-entropy, or the multi-class margin loss (--model svm --loss margin "
+                         "is the reference's SVM)")
     ap.add_argument("--dataset", default="mnist", choices=["mnist", "cifar", "lfw", "creditcard"])
     ap.add_argument("--clients", type=int, default=10)
     ap.add_argument("--poisoned", type=int, default=0)
@@ -124,7 +131,7 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     res = run(a.model, a.dataset, a.clients, a.poisoned, a.iters, a.batch, a.lr, a.momentum, 1e-3, a.eval_every,
-              a.dp_epsilon, a.seed, a.device)
+              a.dp_epsilon, a.seed, a.device, loss=a.loss)
     print(json.dumps({k: v for k, v in res.items() if k != "history"}))
     return 0
 

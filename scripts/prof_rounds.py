@@ -1,11 +1,12 @@
 """cProfile of steady-state headline rounds only (the engine built and warmed outside the profile): which Python
 functions and which torch / native calls hold the round's host thread.
 
-    python scripts/prof_rounds.py [--warm 30] [--rounds 200] [--emulate-world N] [--device-sign] [--no-profile]
-                                  [-o out.txt]
+    python scripts/prof_rounds.py [--warm 30] [--rounds 200] [--emulate-world N] [--device-sign] [--model svm]
+                                  [--no-profile] [-o out.txt]
 
 --emulate-world N profiles rank 0 of an N-rank job (bench.py --emulate-world: the collectives filled locally).
---device-sign sets engine.sign_device (the verifiers' signatures from k_schnorr_sign).  --no-profile times the same
+--device-sign sets engine.sign_device (the verifiers' signatures from k_schnorr_sign).  --model svm runs the rounds
+with the margin-loss local step (k_margin_step) instead of k_softmax_step.  --no-profile times the same
 rounds without cProfile.  The last line printed is one JSON summary: ms per round (wall), the round thread's CPU us
 per round, the final drain's parts and the signer's stats.
 """
@@ -32,12 +33,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--emulate-world", type=int, default=0)
     ap.add_argument("--device-sign", action="store_true")
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm"])
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("-o", "--out", default=None)
     a = ap.parse_args()
     comm = Comm.emulated(a.emulate_world) if a.emulate_world > 1 else Comm.init()
     torch.set_num_threads(1)
-    eng = BiscottiEngine(RunConfig(num_nodes=100, seed=0, max_iterations=10**9, host_threads=14, lazy_eval=True), comm)
+    eng = BiscottiEngine(RunConfig(num_nodes=100, seed=0, max_iterations=10**9, host_threads=14, lazy_eval=True), comm,
+                         model=a.model)
     eng.sign_device = a.device_sign
     for _ in range(a.warm):
         eng.run_round()
@@ -63,7 +66,7 @@ def main():
             with open(a.out, "w") as f:
                 f.write(txt)
         print(txt[:6000])
-    summary = {"device_sign": a.device_sign, "profiled": pr is not None, "rounds": a.rounds,
+    summary = {"model": eng.model, "device_sign": a.device_sign, "profiled": pr is not None, "rounds": a.rounds,
                "ms_per_round": 1e3 * (t1 - t0) / a.rounds, "host_thread_us_per_round": 1e6 * (c1 - c0) / a.rounds,
                "drain_parts_ms": getattr(eng, "drain_parts_ms", None),
                "sign_stats": {k: v for k, v in eng.stats.items() if k.startswith("sign_")}}

@@ -955,7 +955,15 @@ extern "C" void* bsc_stream_create_cumask(int skip_every, int* ncu_used) {
     ++used;
   }
   hipStream_t st = nullptr;
-  if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) return nullptr;
+  if (mask.empty() || hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+    // a device whose queues take no CU mask (a virtual function of the GPU, a partition): an ordinary stream
+    // over every CU -- the same work in the same order, the critical path only loses its reserved quarter.
+    // The refused call's error must not stay behind for the next launch check to report.
+    (void)hipGetLastError();
+    st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamDefault) != hipSuccess) return nullptr;
+    used = ncu;
+  }
   if (ncu_used) *ncu_used = used;
   return (void*)st;
 }

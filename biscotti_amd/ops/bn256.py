@@ -462,14 +462,16 @@ def cu_masked_stream(device, skip_every: int = 4):
     """A torch stream bound to (1 - 1/skip_every) of the device's CUs (hipExtStreamCreateWithCUMask).
 
     Long-running speculative MSMs go there so the protocol's critical-path kernels keep a quarter
-    of the CUs to themselves.  Returns (stream, cus_used); the HIP stream lives for the process."""
+    of the CUs to themselves.  Where the device's queues take no CU mask (a virtual function of the GPU)
+    the stream is an ordinary one over every CU.  Returns (stream, cus_used); the HIP stream lives for
+    the process."""
     import ctypes
 
     used = ctypes.c_int(0)
     with torch.cuda.device(device):
         ptr = hip().bsc_stream_create_cumask(int(skip_every), ctypes.byref(used))
     if not ptr:
-        raise RuntimeError("hipExtStreamCreateWithCUMask failed")
+        raise RuntimeError("no side stream: neither hipExtStreamCreateWithCUMask nor hipStreamCreateWithFlags")
     return torch.cuda.ExternalStream(ptr, device=device), used.value
 
 

@@ -280,3 +280,26 @@ def test_fb_entries_agree_with_the_library():
         assert B.windows_for(b0)[1] == B.fb_entries(b0, B.windows_for(b0)[0])
     for b0, nw in [(7, 9), (21, 9), (8, 0)]:
         assert hip().bsc_fb_entries(b0, nw) == -1, (b0, nw)
+
+
+def test_side_stream_with_or_without_a_cu_mask():
+    """cu_masked_stream hands back a stream that runs work: masked to 3/4 of the CUs where the device's queues
+    take a mask, over every CU where they do not -- and a refused mask leaves no error behind for the next
+    launch check (the library's own, or torch's) to report."""
+    from biscotti_amd.native import hip
+    from biscotti_amd.ops import bn256 as B
+    dev = torch.device("cuda", 0)
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    a = torch.arange(64, dtype=torch.int32, device=dev).reshape(8, 8)
+    torch.cuda.synchronize(dev)
+    st, used = B.cu_masked_stream(dev, 4)
+    assert used in (ncu - ncu // 4, ncu)
+    with torch.cuda.stream(st):
+        got = B.fp_op(a, a, 1)   # limbs far below the modulus: the field sum is the limb-wise sum
+        twice = a + a
+    st.synchronize()
+    assert torch.equal(got, twice) and torch.equal(twice.cpu(), 2 * a.cpu())
+    del got, twice
+    torch.cuda.synchronize(dev)
+    torch.cuda.empty_cache()
+    assert hip().bsc_stream_destroy(st.cuda_stream) == 0

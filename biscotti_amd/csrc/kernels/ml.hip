@@ -1627,12 +1627,15 @@ extern "C" int bsc_dp_noise(const float* delta, int P, int D, const int* noisers
   return (int)hipGetLastError();
 }
 
+// Single-verifier Multi-Krum (K5a-c): X [n, D] fp32; part [ceil(D/ksplit), npad, npad] f64 scratch with
+// npad = 16 * ceil(n/16); dist [n, n], scores [n] f64; accept [n] int32.  n <= 0: no-op, returns 0;
+// n > 128, D <= 0 or ksplit <= 0: returns -1.
 extern "C" int bsc_krum(const float* X, int n, int D, int ksplit, double* part, double* dist, double* scores,
                         int* accept, int groupsize, int n_accept, void* stream) {
   if (n <= 0) return 0;
-  if (n > 128) return -1;
+  if (n > 128 || D <= 0 || ksplit <= 0) return -1;   // nothing is launched or written
   const int tiles = (n + 15) / 16;
-  const int nsplit = (D + ksplit - 1) / ksplit;
+  const int nsplit = (int)(((long long)D + ksplit - 1) / ksplit);
   hipLaunchKernelGGL(k_gram_f64, dim3(tiles, tiles, nsplit), dim3(64), 0, (hipStream_t)stream, X, n, D, ksplit,
                      part);
   hipLaunchKernelGGL(k_krum_scores, dim3(n), dim3(64), 0, (hipStream_t)stream, part, nsplit, n, tiles * 16,

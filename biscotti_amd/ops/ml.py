@@ -326,6 +326,8 @@ def krum_async(X, groupsize: int, n_accept: int, ksplit: int = 256, on_accept=No
     selection kernel is queued (e.g. to cancel or aggregate speculative work on the device)."""
     n, D = X.shape
     assert X.device.type == "cuda" and 0 < n <= 128, "krum kernel handles 1..128 updates per verifier"
+    if D <= 0 or ksplit <= 0:
+        raise ValueError(f"krum needs D > 0 and ksplit > 0 (D = {D}, ksplit = {ksplit})")
     tiles = (n + 15) // 16
     nsplit = (D + ksplit - 1) // ksplit
     part = torch.empty((nsplit, tiles * 16, tiles * 16), dtype=torch.float64, device=X.device)

@@ -4,6 +4,8 @@
 //       fixed-point quantisation -- one workgroup per virtual peer
 //       (ML/Pytorch/client.py:38-65, client_obj.py:73-77, DistSys/kyber.go:698-710); the same body under the
 //       multi-class margin loss is the SVM task's step (k_margin_step; svm_model.py, client.py:28)
+//   K1t top-k sparsification of the step's rows: per-row radix select on the fp32 magnitudes, in place
+//       (ML/code/linear_model.py:48-88)
 //   K3  batched logistic-regression step with DP noise at source (ML/code/logistic_model.py:92-140)
 //   K4  counter-based Gaussian DP noise, averaged over each worker's noisers, added to the delta
 //       (client_obj.py:42-67,97-98; DistSys/main.go:1592-1660,1530-1537)
@@ -281,6 +283,146 @@ extern "C" __global__ void __launch_bounds__(SM_THREADS) k_margin_step(
     long long* qdelta, float* loss, int lo, int* ones, int nones) {
   linear_step_body<MarginLoss>(X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, delta,
                                qdelta, loss, lo, ones, nones);
+}
+
+// =====================================================================================
+// K1t: top-k sparsification of the step's rows, in place (the reference's theta, ML/code/linear_model.py:48-88).
+// Row p keeps its k entries of largest fp32 magnitude -- key(j) = bits(delta[j]) & 0x7fffffff, monotone as an
+// integer; ties at the k-th key are kept in ascending index order -- and every other entry becomes delta = 0.0f,
+// qdelta = 0.  An exact selection, not a sort: an MSB-first radix select over 8-bit digits.
+//   load    the row's keys into LDS when they fit (KEYS_IN_LDS; else every pass re-reads the L2-hot row)
+//   select  at most 4 passes.  Each wave counts the digit of the keys still matching the chosen prefix into its own
+//           256-bin LDS histogram (integer atomics: the counts do not depend on order); wave 0 merges the four, one
+//           lane per 4 bins, suffix-scans them with __shfl_down and picks the bin that holds the r-th largest
+//           candidate; r becomes the number still to take from that bin.  A bin with exactly r keys ends the
+//           passes: all of it is kept
+//   write   in index order, 256 entries at a time: keep key > T; of the keys == T (T = the prefix, under the mask
+//           of the digits chosen) the first r by index -- __ballot / __popcll ranks inside a wave, the waves'
+//           counts through LDS, a running base across chunks, dropped once the r ties are placed.  The zeros are
+//           plain stores, 512 contiguous bytes of qdelta per wave.  kept[p] (optional) = the row's non-zero qdelta
+//           entries afterwards, one store per row.
+// One 256-thread workgroup per row, no global atomics: two runs give the same bytes.
+// =====================================================================================
+constexpr int TK_THREADS = 256;
+constexpr int TK_WAVES = TK_THREADS / 64;
+constexpr int TK_LDS_KEYS = 14336;   // 56 KiB of keys beside the 4 KiB of histograms: inside the default 64 KiB
+
+namespace {
+template <bool KEYS_IN_LDS>
+__device__ __forceinline__ void topk_row_body(float* delta, long long* qdelta, int D, int k, int* kept) {
+  extern __shared__ uint32_t tk_keys[];             // [D] when KEYS_IN_LDS, else unused (0 bytes)
+  __shared__ unsigned int hist[TK_WAVES][256];
+  __shared__ unsigned int sel[3];                   // the chosen bin, the r left inside it, the bin's count
+  __shared__ unsigned int wcnt[2][TK_WAVES];        // the final pass's ties per wave, double-buffered
+  __shared__ int nz_w[TK_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* drow = delta + (size_t)blockIdx.x * D;
+  long long* qrow = qdelta + (size_t)blockIdx.x * D;
+  const uint32_t* bits = reinterpret_cast<const uint32_t*>(drow);
+  auto key_at = [&](int j) -> uint32_t { return KEYS_IN_LDS ? tk_keys[j] : (bits[j] & 0x7fffffffu); };
+
+  if (KEYS_IN_LDS) {
+    for (int j = tid; j < D; j += TK_THREADS) tk_keys[j] = bits[j] & 0x7fffffffu;
+  }
+  uint32_t prefix = 0, mask = 0;   // candidates: (key & mask) == prefix
+  unsigned int r = (unsigned int)k;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = tid; i < TK_WAVES * 256; i += TK_THREADS) (&hist[0][0])[i] = 0;
+    __syncthreads();               // (also: the keys are in LDS before the first pass reads them)
+    for (int j = tid; j < D; j += TK_THREADS) {
+      const uint32_t key = key_at(j);
+      if ((key & mask) == prefix) atomicAdd(&hist[wave][(key >> shift) & 0xffu], 1u);
+    }
+    __syncthreads();
+    if (wave == 0) {
+      unsigned int c[4], t = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        c[i] = 0;
+#pragma unroll
+        for (int w = 0; w < TK_WAVES; ++w) c[i] += hist[w][4 * lane + i];
+        t += c[i];
+      }
+      unsigned int s = t;          // inclusive suffix sum over the lanes: candidates in bins >= 4 * lane
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned int v = __shfl_down(s, o);
+        if (lane + o < 64) s += v;
+      }
+      unsigned int above = s - t;  // candidates in bins above this lane's four
+#pragma unroll
+      for (int i = 3; i >= 0; --i) {
+        if (above < r && r <= above + c[i]) {   // true for exactly one bin of one lane (r <= the candidates)
+          sel[0] = 4u * lane + i;
+          sel[1] = r - above;
+          sel[2] = c[i];
+        }
+        above += c[i];
+      }
+    }
+    __syncthreads();
+    prefix |= sel[0] << shift;
+    mask |= 0xffu << shift;
+    r = sel[1];
+    if (sel[2] == r) break;        // the whole bin is kept: no tie to break below this digit
+  }
+
+  // keep (key & mask) > prefix, and the first r of (key & mask) == prefix by index
+  unsigned int base = 0;           // ties seen in the chunks before this one (the same in every thread)
+  int nz = 0, buf = 0;
+  for (int j0 = 0; j0 < D; j0 += TK_THREADS) {
+    const int j = j0 + tid;
+    const bool valid = j < D;
+    const uint32_t km = valid ? (key_at(j) & mask) : 0u;
+    bool keep = valid && km > prefix;
+    if (base < r) {                // uniform: ties are still being placed
+      const bool tie = valid && km == prefix;
+      const unsigned long long b = __ballot(tie);
+      if (lane == 0) wcnt[buf][wave] = (unsigned int)__popcll(b);
+      __syncthreads();
+      unsigned int before = base, all = 0;
+#pragma unroll
+      for (int w = 0; w < TK_WAVES; ++w) {
+        const unsigned int n = wcnt[buf][w];
+        if (w < wave) before += n;
+        all += n;
+      }
+      keep |= tie && before + (unsigned int)__popcll(b & ((1ull << lane) - 1ull)) < r;
+      base += all;
+      buf ^= 1;                    // the next chunk's counts go to the other buffer: one barrier per chunk
+    }
+    if (valid) {
+      if (!keep) {
+        drow[j] = 0.0f;
+        qrow[j] = 0;
+      } else if (kept != nullptr) {
+        nz += qrow[j] != 0;
+      }
+    }
+  }
+  if (kept != nullptr) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nz += __shfl_down(nz, o);
+    if (lane == 0) nz_w[wave] = nz;
+    __syncthreads();
+    if (tid == 0) {
+      int n = 0;
+      for (int w = 0; w < TK_WAVES; ++w) n += nz_w[w];
+      kept[blockIdx.x] = n;
+    }
+  }
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(TK_THREADS) k_topk_rows(float* delta, long long* qdelta, int D, int k,
+                                                                    int* kept) {
+  topk_row_body<true>(delta, qdelta, D, k, kept);
+}
+
+// the same selection for a row too long for LDS (lfw: 17486 keys): every pass reads the keys from the row
+extern "C" __global__ void __launch_bounds__(TK_THREADS) k_topk_rows_stream(float* delta, long long* qdelta, int D,
+                                                                           int k, int* kept) {
+  topk_row_body<false>(delta, qdelta, D, k, kept);
 }
 
 // =====================================================================================
@@ -1604,6 +1746,20 @@ extern "C" int bsc_margin_step(const float* X, const int* y, const long long* of
   if (P <= 0) return 0;
   hipLaunchKernelGGL(k_margin_step, dim3(P), dim3(SM_THREADS), 0, (hipStream_t)stream, X, y, off, ntrain, pid, W, D_IN,
                      D_OUT, B, P, seed, iteration, max_norm, qscale, delta, qdelta, loss, lo, ones, nones);
+  return (int)hipGetLastError();
+}
+
+// K1t on delta fp32 [P, D] / qdelta int64 [P, D] in place; kept (nullable) int32 [P].  k == D keeps everything:
+// nothing is launched (and kept is not written).
+extern "C" int bsc_topk_rows(float* delta, long long* qdelta, int P, int D, int k, int* kept, void* stream) {
+  if (D <= 0 || k < 1 || k > D) return -1;
+  if (P <= 0 || k == D) return 0;
+  if (D <= TK_LDS_KEYS)
+    hipLaunchKernelGGL(k_topk_rows, dim3(P), dim3(TK_THREADS), (size_t)D * sizeof(uint32_t), (hipStream_t)stream,
+                       delta, qdelta, D, k, kept);
+  else
+    hipLaunchKernelGGL(k_topk_rows_stream, dim3(P), dim3(TK_THREADS), 0, (hipStream_t)stream, delta, qdelta, D, k,
+                       kept);
   return (int)hipGetLastError();
 }
 

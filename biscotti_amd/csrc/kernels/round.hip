@@ -52,6 +52,7 @@ struct PreSlot {  // one slot of the pre-step's output ring
 struct TaskCfg {  // the softmax task's resident data and the pre-step's constants
   int bound = 0;
   int loss = 0;   // the local step's loss: 0 cross-entropy (k_softmax_step), 1 margin (k_margin_step)
+  int topk = 0;   // entries each row of the step keeps (k_topk_rows behind the step); 0: all of them, no launch
   hipStream_t gram;
   const float* X;
   const int *y, *ntrain, *pid, *rows_arange;
@@ -500,6 +501,7 @@ extern "C" int bsc_round_bind_task(void* ctx, void* gram_stream, const float* X,
   t.kchunk = kchunk;
   t.counters = counters;
   t.loss = 0;
+  t.topk = 0;
   t.bound = 1;
   return 0;
 }
@@ -510,6 +512,16 @@ extern "C" int bsc_round_task_loss(void* ctx, int loss) {
   RoundCtx* c = (RoundCtx*)ctx;
   if (c == nullptr || !c->task.bound || loss < 0 || loss > 1) return -1;
   c->task.loss = loss;
+  return 0;
+}
+
+// The bound task's top-k sparsification (0: off, the default of every bind; k: each row of the step keeps its k
+// largest-magnitude entries): the pre-step queues k_topk_rows right behind the step, before ev_step, so the
+// commitments, the shares and the Gram all read the sparsified rows.
+extern "C" int bsc_round_task_topk(void* ctx, int k) {
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || !c->task.bound || k < 0 || k > c->d) return -1;
+  c->task.topk = k;
   return 0;
 }
 
@@ -596,6 +608,7 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
   RC_CHECK((t.loss == 1 ? bsc_margin_step : bsc_softmax_step)(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B,
                                                               t.P, t.seed, it, t.max_norm, t.qs, p.delta, p.qdelta,
                                                               p.loss, t.lo, ones, c->spec_cap, gs));
+  if (t.topk > 0) RC_CHECK(bsc_topk_rows(p.delta, p.qdelta, t.P, c->d, t.topk, nullptr, gs));
   RC_CHECK(hipEventRecord(p.ev_step, gs));
   RC_CHECK(hipStreamWaitEvent(c->bg, p.ev_step, 0));
   RC_CHECK(bsc_shares_msm(p.qdelta, c->d, t.rows_arange, t.P, c->tbl_pk, t.tbl_wb, c->poly, c->T, c->b0, c->nw, 1,

@@ -24,6 +24,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--model", default="softmax", choices=["softmax", "svm"],
                     help="softmax regression, or svm: the same linear scorer under the multi-class margin loss "
                          "(mnist and lfw)")
+    ap.add_argument("--topk", type=float, default=1.0, metavar="THETA",
+                    help="top-k sparsified updates: every worker keeps the int(d * THETA) largest-magnitude entries "
+                         "of its update (mnist and lfw, 0 < THETA <= 1, 1 = off)")
     return ap
 
 
@@ -47,7 +50,7 @@ def main(argv=None) -> int:
     from .protocol.fedsys import FedSysEngine
 
     comm = Comm.init(device=cfg.device)
-    eng = FedSysEngine(cfg, comm, model=ns.model)
+    eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

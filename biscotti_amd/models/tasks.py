@@ -25,9 +25,11 @@ class SoftmaxTask:
 
     def __init__(self, peers: range, num_peers: int, device, seed: int, poisoned: set[int] | None = None,
                  batch_size: int = 10, data_dir: str | None = None, federation: D.MnistFederation | None = None,
-                 dims: tuple | None = None, loss: str = "ce"):
+                 dims: tuple | None = None, loss: str = "ce", topk: float = 1.0):
         if loss not in ("ce", "margin"):
             raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
+        if not 0.0 < topk <= 1.0:
+            raise ValueError(f"topk is the fraction of an update's entries a peer keeps, 0 < topk <= 1, not {topk!r}")
         # "margin": the same linear scorer trained as SVMModel (svm_model.py under nn.MultiLabelMarginLoss with
         # the single target, client.py:28); evaluation, train_error and roni_rows are argmax-based: the same
         self.loss = loss
@@ -40,6 +42,13 @@ class SoftmaxTask:
         self.batch = batch_size
         self.seed = seed
         self.nparam = self.d_out * self.d_in + self.d_out
+        # top-k sparsified updates (the reference's theta, linear_model.py:48-88): step() keeps each row's
+        # k = int(d * topk) largest-magnitude entries and zeroes the rest (K.topk_rows_), with no error feedback, so
+        # the step stays a function of (W, peer, iteration).  topk_k = 0: off (topk == 1), nothing is launched
+        k = int(self.nparam * topk)
+        if k < 1:
+            raise ValueError(f"topk {topk!r} keeps no entry of a {self.nparam}-wide update")
+        self.topk_k = k if k < self.nparam else 0
         poisoned = poisoned or set()
         Xs, ys, offs, ns = [], [], [], []
         o = 0
@@ -89,6 +98,8 @@ class SoftmaxTask:
         delta, qdelta, loss = step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out, self.batch,
                                    self.seed, iteration, 100.0, 1e4, lo=self.peers[0])
         self.last_loss = loss
+        if self.topk_k:
+            K.topk_rows_(delta, qdelta, self.topk_k)
         return delta, qdelta
 
     def evaluate(self, W: torch.Tensor) -> dict:
@@ -258,14 +269,19 @@ class LogisticTask:
 MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 
-def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax", **kw):
+def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax",
+              topk: float = 1.0, **kw):
     """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
-    loss="margin"); creditcard has its logistic model only."""
+    loss="margin"); creditcard has its logistic model only.  topk < 1: mnist / lfw's peers send top-k sparsified
+    updates (SoftmaxTask's topk)."""
     if model not in MODELS:
         raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
     if model == "svm" and dataset == "creditcard":
         raise ValueError("model 'svm' needs a multi-class dataset (mnist, lfw): creditcard trains its logistic model")
+    if topk != 1.0 and dataset == "creditcard":
+        raise ValueError("topk < 1 needs mnist or lfw: creditcard adds its noise at the source, its updates are dense")
     loss = "margin" if model == "svm" else "ce"
+    kw["topk"] = topk
     if dataset == "mnist":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)

@@ -601,6 +601,8 @@ class NativeSecAgg:
                                          U2, kchunk, _ptr(gram_counters)), "round_bind_task")
         if getattr(task, "loss", "ce") == "margin":   # the pre-step queues k_margin_step (a bind resets it to CE)
             _check(hip().bsc_round_task_loss(self.ctx, 1), "round_task_loss")
+        if getattr(task, "topk_k", 0):   # the pre-step queues k_topk_rows behind the step (a bind resets it to off)
+            _check(hip().bsc_round_task_topk(self.ctx, task.topk_k), "round_task_topk")
 
         def ev():
             e = torch.cuda.Event()

@@ -170,6 +170,35 @@ def margin_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_
     return _linear_step("margin_step", X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo)
 
 
+# ---------------------------------------------------------------------------- K1t top-k rows
+def topk_rows_(delta, qdelta, k: int, kept=None):
+    """Top-k sparsification of the step's rows, in place: row p keeps its k entries of largest fp32 magnitude and
+    every other entry becomes delta = 0.0, qdelta = 0 (k_topk_rows; the reference's theta, linear_model.py:48-88).
+
+    delta fp32 [P, D], qdelta int64 [P, D].  Key of entry j: bits(delta[j]) & 0x7fffffff as a uint32; the kept set
+    is the first k of the stable order (key descending, index ascending), so ties at the k-th key go to the lower
+    indices.  k == D keeps everything (nothing runs).  kept int32 [P], optional: the non-zero qdelta entries each
+    row is left with.  Returns (delta, qdelta)."""
+    P, D = delta.shape
+    if not 1 <= k <= D:
+        raise ValueError(f"top-k keeps 1..{D} entries of a row, not {k}")
+    assert delta.dtype == torch.float32 and qdelta.dtype == torch.int64 and qdelta.shape == delta.shape
+    assert kept is None or (kept.dtype == torch.int32 and kept.numel() == P)
+    if delta.device.type == "cuda":
+        _check(hip().bsc_topk_rows(_p(delta), _p(qdelta), P, D, int(k), _p(kept), _stream()), "topk_rows")
+        return delta, qdelta
+    assert delta.is_contiguous() and qdelta.is_contiguous()
+    if k < D and P > 0:
+        d, q = delta.numpy(), qdelta.numpy()   # views: the writes below land in the tensors
+        key = (d.view(np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+        drop = np.argsort(-key, axis=1, kind="stable")[:, k:]
+        np.put_along_axis(d, drop, np.float32(0.0), axis=1)
+        np.put_along_axis(q, drop, np.int64(0), axis=1)
+    if kept is not None and k < D:
+        kept.copy_(torch.count_nonzero(qdelta, dim=1))
+    return delta, qdelta
+
+
 # ---------------------------------------------------------------------------- K3 logistic step
 def logreg_step(X, y, off, nrows, pid, W, B, seed, calls, alpha, lammy, sigma, qscale=1e4):
     """Batched logistic-regression step (creditcard path), DP noise at source when sigma > 0.

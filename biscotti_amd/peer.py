@@ -58,6 +58,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the ledger's model: softmax regression, or svm -- the same linear scorer under the "
                          "multi-class margin loss (k_margin_step; mnist and lfw).  A chain does not record it: "
                          "--resume needs the same --model")
+    ap.add_argument("--topk", type=float, default=1.0, metavar="THETA",
+                    help="top-k sparsified updates: every peer keeps the int(d * THETA) largest-magnitude entries of "
+                         "its update and zeroes the rest (k_topk_rows; mnist and lfw, 0 < THETA <= 1, 1 = off).  A "
+                         "chain does not record it: --resume needs the same --topk")
     return ap
 
 
@@ -86,7 +90,7 @@ def main(argv=None) -> int:
     from .protocol.engine import BiscottiEngine
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
-    eng = BiscottiEngine(cfg, comm, model=ns.model)
+    eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk)
     eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
@@ -158,7 +162,7 @@ def _rpc_peer_main(cfg, ns) -> int:
         addrs = [f"127.0.0.1:{8000 + i}" for i in range(cfg.num_nodes)]
     cfg = dataclasses.replace(cfg, device="cpu")
     peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0,
-                   model=ns.model)
+                   model=ns.model, topk=ns.topk)
     try:
         import time
 

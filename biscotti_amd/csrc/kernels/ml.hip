@@ -286,6 +286,210 @@ extern "C" __global__ void __launch_bounds__(SM_THREADS) k_margin_step(
 }
 
 // =====================================================================================
+// K1e: E local SGD steps of the same linear scorer per round (FedAvg-style local work, --local-steps E).
+//   a_0 = 0;  step e: w_e = (float)W + a_e, minibatch e (Philox tag 0x5EED ^ (e << 16): step 0 draws K1's rows),
+//   g_e = d(mean loss)/dw at w_e, c_e = min(1, max_norm / (||g_e|| + 1e-6)), a_{e+1} = a_e - lr c_e g_e;
+//   delta = a_E (not clipped again), qdelta = quantize(delta), loss = the last step's mean row loss.
+// One 256-thread workgroup per peer; what differs from K1:
+//   a       the accumulated update stays resident for all E steps: in LDS when nparam <= LS_LDS_A (mnist: 7850
+//           floats), else in the peer's own delta row, which no other workgroup touches and which stays L2-hot
+//           (A_IN_LDS = false; lfw: 17486 floats)
+//   draws   lane e of wave 0 draws step e's minibatch, all E draws at once in front of step 0 (E <= 64)
+//   tile    the minibatch rows are staged LS_KT = 256 features at a time, rows LS_KS = LS_KT + 20 floats apart: the
+//           16 rows of a logits operand fall into 16 different bank groups
+//   logits  f32 MFMA 16x16x4 with B = (float)W[c][k] + a[c][k] formed in registers (W fp64 from L2 every step).  The
+//           A operand of the Gram x_s.x_t of the minibatch rows is that same register as A and B: the Gram rides in
+//           the same K-tile pass, one more MFMA per k step and no more LDS reads
+//   clip    for a linear scorer ||g||^2 = sum_{s,t} (G_s.G_t)(x_s.x_t + 1) (dW = G^T x, db = sum_s G_s), so c_e is
+//           known before dW exists: one (s, t) term per thread, combined in fp64 in a fixed order
+//   dW      the MFMA pass (M = classes, N = k tile, K = samples) adds -lr c_e dW straight into a: every entry of a
+//           is owned by one lane, there is no raw-gradient scratch and no second scaling pass
+//   write   one pass at the end: delta (when a lived in LDS) and qdelta
+// LDS: 17664 B tile + 8 KiB of per-wave partials + 4 KiB of draws + 1 KiB G = 31016 B static, plus at most 32 KiB
+// of a (dynamic) = 62.3 KiB: inside the default 64 KiB, so no attribute is set at launch (a wider tile would save
+// barriers, but mnist's a would no longer fit beside it without the opt-in).
+// No atomics, no reduction whose order depends on timing: two runs give the same bytes.
+// =====================================================================================
+constexpr int LS_KT = 256;
+constexpr int LS_KS = LS_KT + 20;
+constexpr int LS_LDS_A = 8192;
+constexpr int LS_MAX_E = 64;
+// scalar fp32 code only in the new kernels (no packed fp32 instructions)
+#define BSC_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+namespace {
+template <class Loss, bool A_IN_LDS>
+BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_local_steps(
+    const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
+    int D_OUT, int B, int P, unsigned long long seed, int iteration, float max_norm, double qscale, int E, float lr,
+    float* delta, long long* qdelta, float* loss, int lo, int* ones, int nones) {
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  if (ones != nullptr && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < nones; i += blockDim.x) ones[i] = 1;
+  extern __shared__ float ls_a[];         // [nparam] when A_IN_LDS, else unused (0 bytes)
+  __shared__ float xs[16 * LS_KS];        // one K tile of the minibatch rows, transformed; rows >= Bq are zero
+  __shared__ float red[4][16][16];        // per-wave partial logits [s][c]
+  __shared__ float gram[4][16][16];       // per-wave partial Gram [s][t] of the transformed rows
+  __shared__ float G[16][16];             // d(mean loss) / d(logits)
+  __shared__ int bidx[LS_MAX_E][16];      // every step's minibatch
+  __shared__ double nrm[SM_THREADS / 64];
+  __shared__ float scale_sh;
+  const int p = blockIdx.x;
+  if (p >= P) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  const int li = lo >= 0 ? pid[p] - lo : p;
+  const long long offp = off[li];
+  const int n = ntrain[li];
+  const int Bq = min(B, n);
+  float* dst = delta + (size_t)p * nparam;
+  float* a = A_IN_LDS ? ls_a : dst;
+  // 1. the E minibatches (K1's draw under step e's tag), one lane per step; a_0 = 0
+  if (tid < E) {
+    int cnt = 0;
+    uint32_t ctr = 0;
+    const uint32_t tag = 0x5EEDu ^ ((uint32_t)tid << 16);
+    while (cnt < Bq) {
+      u4 r = philox(u4{(uint32_t)pid[p], (uint32_t)iteration, ctr++, tag}, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (cnt >= Bq) break;
+        const int c = (int)((q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w) % (uint32_t)n);
+        bool dup = false;
+        for (int t = 0; t < cnt; ++t) dup |= bidx[tid][t] == c;
+        if (!dup) bidx[tid][cnt++] = c;
+      }
+    }
+    for (int t = cnt; t < 16; ++t) bidx[tid][t] = -1;
+  }
+  for (int i = tid; i < nparam; i += SM_THREADS) a[i] = 0.f;
+  __syncthreads();
+  const int ktiles = (D_IN + LS_KT - 1) / LS_KT;
+  const int row = lane & 15, kk = lane >> 4;   // MFMA operand coordinates of this lane
+  for (int e = 0; e < E; ++e) {
+    const int* bi = bidx[e];
+    auto stage = [&](int kt) __attribute__((always_inline)) {  // (x - 0.5) / 0.5; zero padding
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      for (int i = tid; i < 16 * kw; i += SM_THREADS) {
+        const int s = i / kw, k = i % kw;
+        float v = 0.f;
+        if (s < Bq) v = (X[(offp + bi[s]) * (long long)D_IN + k0 + k] - 0.5f) * 2.0f;
+        xs[s * LS_KS + k] = v;
+      }
+    };
+    // 2. logits of w_e = (float)W + a and the rows' Gram, in one pass over the K tiles (the 4 waves split a tile)
+    {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f}, gacc = {0.f, 0.f, 0.f, 0.f};
+      for (int kt = 0; kt < ktiles; ++kt) {
+        const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+        __syncthreads();  // the tile's last readers (the previous tile, or the previous step's dW pass) are done
+        stage(kt);
+        __syncthreads();
+        const int ksteps = (kw + 3) / 4;
+        const int per = (ksteps + 3) / 4;
+        for (int st = wid * per; st < min(ksteps, (wid + 1) * per); ++st) {
+          const int k = st * 4 + kk;
+          const bool in = k < kw;
+          const float av = in ? xs[row * LS_KS + k] : 0.f;
+          float bv = 0.f;
+          if (in && row < D_OUT) bv = (float)W[row * D_IN + k0 + k] + a[row * D_IN + k0 + k];
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+          gacc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, av, gacc, 0, 0, 0);   // A[s][k] and B[k][t]: one register
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        red[wid][kk * 4 + r][row] = acc[r];
+        gram[wid][kk * 4 + r][row] = gacc[r];
+      }
+    }
+    __syncthreads();
+    // 3. the loss and G on rows s < Bq (one thread per row), as K1
+    if (tid < 16) {
+      const int s = tid;
+      if (s < Bq) {
+        float* lg = red[0][s];   // the row's logits, summed in place (LDS: the label indexes them)
+        for (int c = 0; c < D_OUT; ++c)
+          lg[c] = red[0][s][c] + red[1][s][c] + red[2][s][c] + red[3][s][c] +
+                  ((float)W[D_OUT * D_IN + c] + a[D_OUT * D_IN + c]);
+        const float l = Loss::row(lg, D_OUT, y[offp + bi[s]], Bq, G[s]);
+        for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
+        red[1][s][0] = l;
+      } else {
+        for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
+      }
+    }
+    __syncthreads();
+    if (tid == 0 && e == E - 1) {
+      float l = 0.f;
+      for (int s = 0; s < Bq; ++s) l += red[1][s][0];
+      loss[p] = l / (float)max(Bq, 1);
+    }
+    // 4. the clip coefficient from G and the Gram: thread (s, t) holds (G_s.G_t)(x_s.x_t + 1)
+    {
+      const int s = tid >> 4, t = tid & 15;
+      double gg = 0.0;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) gg += (double)G[s][c] * (double)G[t][c];
+      const float xx = gram[0][s][t] + gram[1][s][t] + gram[2][s][t] + gram[3][s][t];
+      double sq = gg * ((double)xx + 1.0);
+      for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+      if (lane == 0) nrm[wid] = sq;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const float tot = (float)sqrt(fmax(nrm[0] + nrm[1] + nrm[2] + nrm[3], 0.0));
+      const float coef = max_norm / (tot + 1e-6f);
+      scale_sh = coef < 1.f ? coef : 1.f;
+    }
+    __syncthreads();
+    const float sc = -(lr * scale_sh);
+    // 5. a += sc * dW, dW[c][k] = sum_s G[s][c] xs[s][k] via f32 MFMA; the last tile is still resident: it goes first
+    for (int q = 0; q < ktiles; ++q) {
+      const int kt = (ktiles - 1 + q) % ktiles;
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      if (q > 0) {
+        __syncthreads();
+        stage(kt);
+        __syncthreads();
+      }
+      const int ntiles = (kw + 15) / 16;
+      for (int t = wid; t < ntiles; t += 4) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const int k = t * 16 + row;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const int s = ks * 4 + kk;
+          const float av = G[s][row];  // A[c = row][s]
+          const float bv = (k < kw) ? xs[s * LS_KS + k] : 0.f;
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = kk * 4 + r;
+          if (c < D_OUT && k < kw) a[c * D_IN + k0 + k] += sc * acc[r];
+        }
+      }
+    }
+    if (tid < D_OUT) {
+      float db = 0.f;
+      for (int s = 0; s < 16; ++s) db += G[s][tid];
+      a[D_OUT * D_IN + tid] += sc * db;
+    }
+    // (the next step's first barrier, or the one below, orders these writes of a before their readers)
+  }
+  __syncthreads();
+  // 6. delta = a_E, quantised like updateFloatToInt
+  long long* qd = qdelta + (size_t)p * nparam;
+  for (int i = tid; i < nparam; i += SM_THREADS) {
+    const float v = a[i];
+    if (A_IN_LDS) dst[i] = v;
+    qd[i] = quantize(v, qscale);
+  }
+}
+}  // namespace
+
+// =====================================================================================
 // K1t: top-k sparsification of the step's rows, in place (the reference's theta, ML/code/linear_model.py:48-88).
 // Row p keeps its k entries of largest fp32 magnitude -- key(j) = bits(delta[j]) & 0x7fffffff, monotone as an
 // integer; ties at the k-th key are kept in ascending index order -- and every other entry becomes delta = 0.0f,
@@ -1747,6 +1951,42 @@ extern "C" int bsc_margin_step(const float* X, const int* y, const long long* of
   hipLaunchKernelGGL(k_margin_step, dim3(P), dim3(SM_THREADS), 0, (hipStream_t)stream, X, y, off, ntrain, pid, W, D_IN,
                      D_OUT, B, P, seed, iteration, max_norm, qscale, delta, qdelta, loss, lo, ones, nones);
   return (int)hipGetLastError();
+}
+
+namespace {
+template <class Loss>
+int local_steps_launch(hipStream_t s, int nparam, const float* X, const int* y, const long long* off, const int* ntrain,
+                       const int* pid, const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed,
+                       int iteration, float max_norm, double qscale, int E, float lr, float* delta, long long* qdelta,
+                       float* loss, int lo, int* ones, int nones) {
+  if (nparam <= LS_LDS_A)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_local_steps<Loss, true>), dim3(P), dim3(SM_THREADS),
+                       (size_t)nparam * sizeof(float), s, X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration,
+                       max_norm, qscale, E, lr, delta, qdelta, loss, lo, ones, nones);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_local_steps<Loss, false>), dim3(P), dim3(SM_THREADS), 0, s, X, y, off, ntrain,
+                       pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, E, lr, delta, qdelta, loss, lo,
+                       ones, nones);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+// K1e: E local steps at rate lr under loss 0 (cross-entropy) or 1 (margin); K1's arguments and limits otherwise.
+// a lives in LDS up to LS_LDS_A parameters, in the delta rows beyond.
+extern "C" int bsc_local_steps(int loss, const float* X, const int* y, const long long* off, const int* ntrain,
+                               const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
+                               unsigned long long seed, int iteration, float max_norm, double qscale, int E, float lr,
+                               float* delta, long long* qdelta, float* loss_out, int lo, int* ones, int nones,
+                               void* stream) {
+  if (D_IN <= 0 || D_OUT > 16 || B > 16 || E < 1 || E > LS_MAX_E || !(lr > 0.f) || loss < 0 || loss > 1) return -1;
+  if (P <= 0) return 0;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  return loss == 1 ? local_steps_launch<MarginLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN, D_OUT,
+                                                    B, P, seed, iteration, max_norm, qscale, E, lr, delta, qdelta,
+                                                    loss_out, lo, ones, nones)
+                   : local_steps_launch<CrossEntropyLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN,
+                                                          D_OUT, B, P, seed, iteration, max_norm, qscale, E, lr, delta,
+                                                          qdelta, loss_out, lo, ones, nones);
 }
 
 // K1t on delta fp32 [P, D] / qdelta int64 [P, D] in place; kept (nullable) int32 [P].  k == D keeps everything:

@@ -53,6 +53,8 @@ struct TaskCfg {  // the softmax task's resident data and the pre-step's constan
   int bound = 0;
   int loss = 0;   // the local step's loss: 0 cross-entropy (k_softmax_step), 1 margin (k_margin_step)
   int topk = 0;   // entries each row of the step keeps (k_topk_rows behind the step); 0: all of them, no launch
+  int local_E = 1;       // local SGD steps per round; above 1 the pre-step queues k_local_steps instead of the step
+  float local_lr = 1.f;  // their rate
   hipStream_t gram;
   const float* X;
   const int *y, *ntrain, *pid, *rows_arange;
@@ -502,6 +504,8 @@ extern "C" int bsc_round_bind_task(void* ctx, void* gram_stream, const float* X,
   t.counters = counters;
   t.loss = 0;
   t.topk = 0;
+  t.local_E = 1;
+  t.local_lr = 1.f;
   t.bound = 1;
   return 0;
 }
@@ -522,6 +526,16 @@ extern "C" int bsc_round_task_topk(void* ctx, int k) {
   RoundCtx* c = (RoundCtx*)ctx;
   if (c == nullptr || !c->task.bound || k < 0 || k > c->d) return -1;
   c->task.topk = k;
+  return 0;
+}
+
+// The bound task's local work (E = 1, the default of every bind: one step, today's kernels; E > 1: the pre-step queues
+// k_local_steps, E steps at rate lr under the bound loss, and every consumer reads the accumulated update).
+extern "C" int bsc_round_task_local(void* ctx, int E, float lr) {
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || !c->task.bound || E < 1 || E > 64 || !(lr > 0.f)) return -1;
+  c->task.local_E = E;
+  c->task.local_lr = lr;
   return 0;
 }
 
@@ -605,9 +619,14 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
   RC_CHECK(hipEventRecord(c->ev_pre, c->main));
   RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
   if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
-  RC_CHECK((t.loss == 1 ? bsc_margin_step : bsc_softmax_step)(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B,
-                                                              t.P, t.seed, it, t.max_norm, t.qs, p.delta, p.qdelta,
-                                                              p.loss, t.lo, ones, c->spec_cap, gs));
+  if (t.local_E > 1)
+    RC_CHECK(bsc_local_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it,
+                             t.max_norm, t.qs, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss, t.lo, ones,
+                             c->spec_cap, gs));
+  else
+    RC_CHECK((t.loss == 1 ? bsc_margin_step : bsc_softmax_step)(t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out,
+                                                                t.B, t.P, t.seed, it, t.max_norm, t.qs, p.delta,
+                                                                p.qdelta, p.loss, t.lo, ones, c->spec_cap, gs));
   if (t.topk > 0) RC_CHECK(bsc_topk_rows(p.delta, p.qdelta, t.P, c->d, t.topk, nullptr, gs));
   RC_CHECK(hipEventRecord(p.ev_step, gs));
   RC_CHECK(hipStreamWaitEvent(c->bg, p.ev_step, 0));

@@ -27,6 +27,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--topk", type=float, default=1.0, metavar="THETA",
                     help="top-k sparsified updates: every worker keeps the int(d * THETA) largest-magnitude entries "
                          "of its update (mnist and lfw, 0 < THETA <= 1, 1 = off)")
+    ap.add_argument("--local-steps", type=int, default=1, metavar="E",
+                    help="local SGD steps per worker and round, each on a fresh minibatch (k_local_steps; mnist and "
+                         "lfw, 1..64, 1 = the single step)")
+    ap.add_argument("--local-lr", type=float, default=1.0, metavar="ETA", help="the rate of those local steps (> 0)")
     return ap
 
 
@@ -50,7 +54,7 @@ def main(argv=None) -> int:
     from .protocol.fedsys import FedSysEngine
 
     comm = Comm.init(device=cfg.device)
-    eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk)
+    eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

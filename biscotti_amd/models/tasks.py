@@ -25,11 +25,22 @@ class SoftmaxTask:
 
     def __init__(self, peers: range, num_peers: int, device, seed: int, poisoned: set[int] | None = None,
                  batch_size: int = 10, data_dir: str | None = None, federation: D.MnistFederation | None = None,
-                 dims: tuple | None = None, loss: str = "ce", topk: float = 1.0):
+                 dims: tuple | None = None, loss: str = "ce", topk: float = 1.0, local_steps: int = 1,
+                 local_lr: float = 1.0):
         if loss not in ("ce", "margin"):
             raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
         if not 0.0 < topk <= 1.0:
             raise ValueError(f"topk is the fraction of an update's entries a peer keeps, 0 < topk <= 1, not {topk!r}")
+        if isinstance(local_steps, bool) or local_steps != int(local_steps) or \
+                not 1 <= local_steps <= K.LOCAL_STEPS_MAX:
+            raise ValueError(f"local_steps is the number of local SGD steps per round, an integer in "
+                             f"1..{K.LOCAL_STEPS_MAX}, not {local_steps!r}")
+        if not local_lr > 0:
+            raise ValueError(f"local_lr is the rate of the local steps, > 0, not {local_lr!r}")
+        # local work (FedAvg-style): step() runs local_steps SGD steps at rate local_lr from W on fresh minibatches
+        # and sends the accumulated difference (K.local_steps); still a function of (W, peer, iteration).  1: the
+        # single step and its own kernel, whatever local_lr
+        self.local_steps, self.local_lr = int(local_steps), float(local_lr)
         # "margin": the same linear scorer trained as SVMModel (svm_model.py under nn.MultiLabelMarginLoss with
         # the single target, client.py:28); evaluation, train_error and roni_rows are argmax-based: the same
         self.loss = loss
@@ -94,9 +105,14 @@ class SoftmaxTask:
             pid = h2d(peers, torch.int32, self.device)
             if len(self._sel_cache) < 64:
                 self._sel_cache[key] = pid
-        step = K.margin_step if self.loss == "margin" else K.softmax_step
-        delta, qdelta, loss = step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out, self.batch,
-                                   self.seed, iteration, 100.0, 1e4, lo=self.peers[0])
+        if self.local_steps > 1:
+            delta, qdelta, loss = K.local_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
+                                                self.batch, self.seed, iteration, self.local_steps, self.local_lr,
+                                                loss=self.loss, lo=self.peers[0])
+        else:
+            step = K.margin_step if self.loss == "margin" else K.softmax_step
+            delta, qdelta, loss = step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out, self.batch,
+                                       self.seed, iteration, 100.0, 1e4, lo=self.peers[0])
         self.last_loss = loss
         if self.topk_k:
             K.topk_rows_(delta, qdelta, self.topk_k)
@@ -270,18 +286,23 @@ MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 
 def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax",
-              topk: float = 1.0, **kw):
+              topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, **kw):
     """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
     loss="margin"); creditcard has its logistic model only.  topk < 1: mnist / lfw's peers send top-k sparsified
-    updates (SoftmaxTask's topk)."""
+    updates (SoftmaxTask's topk).  local_steps > 1: they run that many local SGD steps per round at rate local_lr
+    (SoftmaxTask's local_steps)."""
     if model not in MODELS:
         raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
     if model == "svm" and dataset == "creditcard":
         raise ValueError("model 'svm' needs a multi-class dataset (mnist, lfw): creditcard trains its logistic model")
     if topk != 1.0 and dataset == "creditcard":
         raise ValueError("topk < 1 needs mnist or lfw: creditcard adds its noise at the source, its updates are dense")
+    if (local_steps != 1 or local_lr != 1.0) and dataset == "creditcard":
+        raise ValueError("local_steps / local_lr need mnist or lfw: creditcard's logistic step is a single noisy step")
     loss = "margin" if model == "svm" else "ce"
     kw["topk"] = topk
+    if dataset != "creditcard":
+        kw["local_steps"], kw["local_lr"] = local_steps, local_lr
     if dataset == "mnist":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)

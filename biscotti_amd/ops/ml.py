@@ -105,9 +105,16 @@ def _margin_rows(logits, lab):
 _LINEAR_STEPS = {"softmax_step": ("bsc_softmax_step", _ce_rows), "margin_step": ("bsc_margin_step", _margin_rows)}
 
 
-def _linear_step(what, X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo):
+LOCAL_STEPS_MAX = 64   # k_local_steps' LS_MAX_E
+
+
+def _linear_step(what, X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo, E=None,
+                 lr=1.0):
     """The local step of the linear scorer under one loss of _LINEAR_STEPS: its launcher on a GPU, on the CPU the
-    torch fp32 path (the minibatch draw, the transform, the clip and the quantisation are the same for every loss)."""
+    torch fp32 path (the minibatch draw, the transform, the clip and the quantisation are the same for every loss).
+    E (None: the single step and its own kernel): E local steps at rate lr, k_local_steps -- step e differentiates
+    the scorer float32(W) + a_e on the minibatch of tag 0x5EED ^ (e << 16), a_{e+1} = a_e - lr * clip(g_e); the
+    accumulated a_E is the update and the loss is the last step's."""
     launcher, loss_rows = _LINEAR_STEPS[what]
     P = pid.numel()
     nparam = d_out * d_in + d_out
@@ -119,9 +126,15 @@ def _linear_step(what, X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteratio
         assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
         assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
         assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
-        _check(getattr(hip(), launcher)(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, d_out, B, P,
-                                        seed & (2**64 - 1), iteration, float(max_norm), float(qscale), _p(delta),
-                                        _p(qdelta), _p(loss), int(lo), None, 0, _stream()), what)
+        if E is None:
+            _check(getattr(hip(), launcher)(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, d_out, B, P,
+                                            seed & (2**64 - 1), iteration, float(max_norm), float(qscale), _p(delta),
+                                            _p(qdelta), _p(loss), int(lo), None, 0, _stream()), what)
+        else:
+            _check(hip().bsc_local_steps(int(what == "margin_step"), _p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W),
+                                         d_in, d_out, B, P, seed & (2**64 - 1), iteration, float(max_norm),
+                                         float(qscale), int(E), float(lr), _p(delta), _p(qdelta), _p(loss), int(lo),
+                                         None, 0, _stream()), "local_steps")
         return delta, qdelta, loss
     Wm = W.to(torch.float32)
     Wt, bt = Wm[: d_out * d_in].view(d_out, d_in), Wm[d_out * d_in:]
@@ -132,18 +145,22 @@ def _linear_step(what, X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteratio
     else:
         offs, ns = off.tolist(), ntrain.tolist()
     for p in range(P):
-        idx = minibatch_indices(pids[p], iteration, ns[p], B, seed)
-        rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
-        xb = (X[rows] - 0.5) / 0.5
-        logits = xb @ Wt.T + bt
-        lossv, g = loss_rows(logits, y[rows].long())
-        dW, db = g.T @ xb, g.sum(0)
-        flat = torch.cat([dW.reshape(-1), db])
-        tot = float(torch.linalg.vector_norm(flat))
-        coef = max_norm / (tot + 1e-6)
-        if coef < 1:
-            flat = flat * coef
-        v = -flat
+        v = None   # a_e, the update accumulated so far
+        for e in range(E or 1):
+            idx = minibatch_indices(pids[p], iteration, ns[p], B, seed, tag=0x5EED ^ (e << 16))
+            rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
+            xb = (X[rows] - 0.5) / 0.5
+            We, be = (Wt, bt) if v is None else (Wt + v[: d_out * d_in].view(d_out, d_in), bt + v[d_out * d_in:])
+            logits = xb @ We.T + be
+            lossv, g = loss_rows(logits, y[rows].long())
+            dW, db = g.T @ xb, g.sum(0)
+            flat = torch.cat([dW.reshape(-1), db])
+            tot = float(torch.linalg.vector_norm(flat))
+            coef = max_norm / (tot + 1e-6)
+            if coef < 1:
+                flat = flat * coef
+            u = -flat if lr == 1.0 else -flat * float(lr)
+            v = u if v is None else v + u
         delta[p] = v
         qdelta[p] = torch.from_numpy((v.double().numpy() * qscale).astype(np.int64))
         loss[p] = lossv
@@ -168,6 +185,21 @@ def margin_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_
     nn.MultiLabelMarginLoss with the single target [y, -1, ...], client.py:28).  Arguments and return values are
     softmax_step's."""
     return _linear_step("margin_step", X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo)
+
+
+def local_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, E, lr, loss="ce", max_norm=100.0,
+                qscale=1e4, lo=-1):
+    """E local SGD steps per peer at rate lr under loss "ce" or "margin" (k_local_steps): step e differentiates the
+    scorer float32(W) + a_e on its own minibatch (Philox tag 0x5EED ^ (e << 16); step 0 draws softmax_step's rows),
+    clips that gradient like softmax_step and adds -lr times it to a.  Returns (delta = a_E fp32 [P, nparam], not
+    clipped again, qdelta int64, loss fp32 [P] of the last step).  E = 1, lr = 1 is softmax_step / margin_step;
+    the other arguments are theirs."""
+    if loss not in ("ce", "margin"):
+        raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
+    if E != int(E) or not 1 <= E <= LOCAL_STEPS_MAX or not lr > 0:
+        raise ValueError(f"local steps: an integer E in 1..{LOCAL_STEPS_MAX} and a rate lr > 0, not E={E!r} lr={lr!r}")
+    return _linear_step("margin_step" if loss == "margin" else "softmax_step", X, y, off, ntrain, pid, W, d_in, d_out, B,
+                        seed, iteration, max_norm, qscale, lo, E=int(E), lr=float(lr))
 
 
 # ---------------------------------------------------------------------------- K1t top-k rows

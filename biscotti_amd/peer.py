@@ -62,6 +62,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="top-k sparsified updates: every peer keeps the int(d * THETA) largest-magnitude entries of "
                          "its update and zeroes the rest (k_topk_rows; mnist and lfw, 0 < THETA <= 1, 1 = off).  A "
                          "chain does not record it: --resume needs the same --topk")
+    ap.add_argument("--local-steps", type=int, default=1, metavar="E",
+                    help="local SGD steps per peer and round, each on a fresh minibatch; the peer sends the accumulated "
+                         "difference (k_local_steps; mnist and lfw, 1..64, 1 = today's single step).  A chain does "
+                         "not record it: --resume needs the same --local-steps and --local-lr")
+    ap.add_argument("--local-lr", type=float, default=1.0, metavar="ETA", help="the rate of those local steps (> 0)")
     return ap
 
 
@@ -90,7 +95,7 @@ def main(argv=None) -> int:
     from .protocol.engine import BiscottiEngine
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
-    eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk)
+    eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr)
     eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
@@ -162,7 +167,7 @@ def _rpc_peer_main(cfg, ns) -> int:
         addrs = [f"127.0.0.1:{8000 + i}" for i in range(cfg.num_nodes)]
     cfg = dataclasses.replace(cfg, device="cpu")
     peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0,
-                   model=ns.model, topk=ns.topk)
+                   model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr)
     try:
         import time
 

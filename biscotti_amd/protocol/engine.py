@@ -78,7 +78,8 @@ class RoundResult:
 
 class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, VrfAuditMixin, SigAuditMixin,
                      FaultsMixin):
-    def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0):
+    def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0,
+                 local_steps: int = 1, local_lr: float = 1.0):
         cfg.validate()
         self.cfg = cfg
         # the ledger's model ("softmax", or "svm": the same scorer under the margin loss; models.make_task).  An
@@ -88,6 +89,9 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         # top-k sparsified updates (models.make_task): the fraction of its entries a peer's update keeps; 1: off.
         # An engine argument like model, and like it not recorded by a chain
         self.topk = topk
+        # local work (models.make_task): SGD steps per peer and round, and their rate; 1: today's single step.
+        # Engine arguments like topk, and like it not recorded by a chain
+        self.local_steps, self.local_lr = local_steps, local_lr
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -127,7 +131,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         poisoned = {p for p in self.local if fsm_probe.is_poisoner(p)}
         colluders = {p for p in range(self.N) if fsm_probe.is_colluder(p)}
         self.colluders = colluders
-        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk, poisoned=poisoned,
+        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk,
+                              local_steps=local_steps, local_lr=local_lr, poisoned=poisoned,
                               batch_size=cfg.batch_size, data_dir=cfg.data_dir, epsilon=cfg.epsilon,
                               colluders=colluders)
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)

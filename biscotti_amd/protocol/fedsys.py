@@ -45,13 +45,15 @@ class FedSysResult:
 
 
 class FedSysEngine:
-    def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0):
+    def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0,
+                 local_steps: int = 1, local_lr: float = 1.0):
         from ..data import dataset_dims
         from ..models import make_task
 
         self.cfg = cfg
         self.model = model   # "softmax" or "svm" (models.make_task), as BiscottiEngine's
         self.topk = topk     # top-k sparsified updates (models.make_task), as BiscottiEngine's; 1: off
+        self.local_steps, self.local_lr = local_steps, local_lr   # local SGD steps per round and their rate; 1: off
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -72,7 +74,8 @@ class FedSysEngine:
         self.d = dataset_dims(cfg.dataset)[0]
         probe = self.R.RoundFSM(pc, self.d)
         poisoned = {p for p in self.local if probe.is_poisoner(p, True)}   # FedSys: >= (Q4)
-        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk, poisoned=poisoned,
+        self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk,
+                              local_steps=local_steps, local_lr=local_lr, poisoned=poisoned,
                               batch_size=cfg.batch_size, data_dir=cfg.data_dir, epsilon=cfg.epsilon,
                               colluders=set())
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)

@@ -490,6 +490,200 @@ BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_local_steps(
 }  // namespace
 
 // =====================================================================================
+// K1p: E DP-SGD steps of the same linear scorer per round (--dp-clip C [--dp-sigma S]; docs/QUIRKS.md Q18): each
+// example's gradient is clipped to C before the minibatch rows are summed, N(0, (S C)^2) is added to the sum, and
+// the sum is divided by the batch size.
+//   a_0 = 0;  step e: w_e = (float)W + a_e, minibatch e (K1e's tags), gamma_s = Bq G_s the row's gradient with
+//   respect to its logits, n_s = ||gamma_s|| sqrt(||x_s||^2 + 1), c_s = min(1, C / (n_s + 1e-6)),
+//   g_e = (1 / Bq) (sum_s c_s gamma_s (x) (x_s, 1) + S C xi_e), a_{e+1} = a_e - lr g_e (no clip of the mean);
+//   xi_e[j] = gauss of philox((j, iteration, peer, 0xD95D ^ (e << 16)), seed);  delta = a_E, qdelta, the last loss.
+// K1e's workgroup, residency of a, draws and 256-feature tile; what is its own:
+//   norms   a row's gradient has rank one, so n_s needs ||x_s||^2 and nothing of dW: every lane squares the A operand
+//           it already holds beside the logits MFMA (one FMA per k step in place of K1e's Gram MFMA), the four kk lane
+//           groups meet through two __shfl_xor, the four waves through rsq[4][16], summed in a fixed order
+//   clip    the row thread that runs Loss::row scales its row of G by c_s in place: the dW pass then sums clipped
+//           rows at K1e's cost, and there is no norm of the whole gradient, no fp64 and no second barrier pair
+//   noise   S > 0 only (a uniform branch): one pass over a per step, one Philox call per entry; the last step's
+//           pass is the final delta / qdelta write
+// LDS: 17664 B tile + 4 KiB of per-wave logits + 256 B of row norms + 4 KiB of draws + 1 KiB G = 27136 B static,
+// plus at most 32 KiB of a (dynamic) = 58.5 KiB: inside the default 64 KiB, no attribute is set at launch.
+// No atomics, no reduction whose order depends on timing: two runs give the same bytes.
+// =====================================================================================
+namespace {
+template <class Loss, bool A_IN_LDS>
+BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_dpsgd_steps(
+    const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
+    int D_OUT, int B, int P, unsigned long long seed, int iteration, double qscale, float clip, float sigma, int E,
+    float lr, float* delta, long long* qdelta, float* loss, int lo, int* ones, int nones) {
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  if (ones != nullptr && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < nones; i += blockDim.x) ones[i] = 1;
+  extern __shared__ float dp_a[];         // [nparam] when A_IN_LDS, else unused (0 bytes)
+  __shared__ float xs[16 * LS_KS];        // one K tile of the minibatch rows, transformed; rows >= Bq are zero
+  __shared__ float red[4][16][16];        // per-wave partial logits [s][c]
+  __shared__ float rsq[4][16];            // per-wave partial ||x_s||^2
+  __shared__ float G[16][16];             // c_s G_s: the clipped rows of d(mean loss) / d(logits)
+  __shared__ int bidx[LS_MAX_E][16];      // every step's minibatch
+  const int p = blockIdx.x;
+  if (p >= P) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  const uint32_t peer = (uint32_t)pid[p];
+  const int li = lo >= 0 ? pid[p] - lo : p;
+  const long long offp = off[li];
+  const int n = ntrain[li];
+  const int Bq = min(B, n);
+  float* dst = delta + (size_t)p * nparam;
+  float* a = A_IN_LDS ? dp_a : dst;
+  const uint32_t k0s = (uint32_t)seed, k1s = (uint32_t)(seed >> 32);
+  // 1. the E minibatches, one lane per step (K1e's draw); a_0 = 0
+  if (tid < E) {
+    int cnt = 0;
+    uint32_t ctr = 0;
+    const uint32_t tag = 0x5EEDu ^ ((uint32_t)tid << 16);
+    while (cnt < Bq) {
+      u4 r = philox(u4{peer, (uint32_t)iteration, ctr++, tag}, k0s, k1s);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (cnt >= Bq) break;
+        const int c = (int)((q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w) % (uint32_t)n);
+        bool dup = false;
+        for (int t = 0; t < cnt; ++t) dup |= bidx[tid][t] == c;
+        if (!dup) bidx[tid][cnt++] = c;
+      }
+    }
+    for (int t = cnt; t < 16; ++t) bidx[tid][t] = -1;
+  }
+  for (int i = tid; i < nparam; i += SM_THREADS) a[i] = 0.f;
+  __syncthreads();
+  const int ktiles = (D_IN + LS_KT - 1) / LS_KT;
+  const int row = lane & 15, kk = lane >> 4;   // MFMA operand coordinates of this lane
+  const bool noisy = sigma > 0.f;              // uniform
+  const float nsc = lr * (sigma * clip / (float)max(Bq, 1));   // what one N(0, 1) draw moves an entry of a by
+  auto xi = [&](int j, int e) __attribute__((always_inline)) {
+    const u4 r = philox(u4{(uint32_t)j, (uint32_t)iteration, peer, 0xD95Du ^ ((uint32_t)e << 16)}, k0s, k1s);
+    return gauss(r.x, r.y);
+  };
+  for (int e = 0; e < E; ++e) {
+    const int* bi = bidx[e];
+    auto stage = [&](int kt) __attribute__((always_inline)) {  // (x - 0.5) / 0.5; zero padding
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      for (int i = tid; i < 16 * kw; i += SM_THREADS) {
+        const int s = i / kw, k = i % kw;
+        float v = 0.f;
+        if (s < Bq) v = (X[(offp + bi[s]) * (long long)D_IN + k0 + k] - 0.5f) * 2.0f;
+        xs[s * LS_KS + k] = v;
+      }
+    };
+    // 2. logits of w_e = (float)W + a and the rows' squared norms, in one pass over the K tiles
+    {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      float xx = 0.f;   // this lane's share of ||x_row||^2: the k of its kk group in its wave's part of each tile
+      for (int kt = 0; kt < ktiles; ++kt) {
+        const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+        __syncthreads();  // the tile's last readers and the last writers of a (dW or noise pass) are done
+        stage(kt);
+        __syncthreads();
+        const int ksteps = (kw + 3) / 4;
+        const int per = (ksteps + 3) / 4;
+        for (int st = wid * per; st < min(ksteps, (wid + 1) * per); ++st) {
+          const int k = st * 4 + kk;
+          const bool in = k < kw;
+          const float av = in ? xs[row * LS_KS + k] : 0.f;
+          float bv = 0.f;
+          if (in && row < D_OUT) bv = (float)W[row * D_IN + k0 + k] + a[row * D_IN + k0 + k];
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+          xx = fmaf(av, av, xx);
+        }
+      }
+      xx += __shfl_xor(xx, 16);
+      xx += __shfl_xor(xx, 32);
+      if (kk == 0) rsq[wid][row] = xx;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wid][kk * 4 + r][row] = acc[r];
+    }
+    __syncthreads();
+    // 3. the loss, G and the clip on rows s < Bq (one thread per row): the row of G leaves scaled by c_s
+    if (tid < 16) {
+      const int s = tid;
+      if (s < Bq) {
+        float* lg = red[0][s];   // the row's logits, summed in place (LDS: the label indexes them)
+        for (int c = 0; c < D_OUT; ++c)
+          lg[c] = red[0][s][c] + red[1][s][c] + red[2][s][c] + red[3][s][c] +
+                  ((float)W[D_OUT * D_IN + c] + a[D_OUT * D_IN + c]);
+        const float l = Loss::row(lg, D_OUT, y[offp + bi[s]], Bq, G[s]);
+        float gg = 0.f;
+        for (int c = 0; c < D_OUT; ++c) gg = fmaf(G[s][c], G[s][c], gg);
+        const float x2 = (rsq[0][s] + rsq[1][s]) + (rsq[2][s] + rsq[3][s]);
+        const float ns = (float)Bq * sqrtf(gg) * sqrtf(x2 + 1.f);   // ||gamma_s (x) (x_s, 1)||, gamma_s = Bq G_s
+        const float coef = clip / (ns + 1e-6f);
+        if (coef < 1.f)
+          for (int c = 0; c < D_OUT; ++c) G[s][c] *= coef;
+        for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
+        red[1][s][0] = l;
+      } else {
+        for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
+      }
+    }
+    __syncthreads();
+    if (tid == 0 && e == E - 1) {
+      float l = 0.f;
+      for (int s = 0; s < Bq; ++s) l += red[1][s][0];
+      loss[p] = l / (float)max(Bq, 1);
+    }
+    const float sc = -lr;
+    // 4. a += sc * dW, dW[c][k] = sum_s G[s][c] xs[s][k] (clipped rows) via f32 MFMA; the resident last tile goes first
+    for (int q = 0; q < ktiles; ++q) {
+      const int kt = (ktiles - 1 + q) % ktiles;
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      if (q > 0) {
+        __syncthreads();
+        stage(kt);
+        __syncthreads();
+      }
+      const int ntiles = (kw + 15) / 16;
+      for (int t = wid; t < ntiles; t += 4) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const int k = t * 16 + row;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const int s = ks * 4 + kk;
+          const float av = G[s][row];  // A[c = row][s]
+          const float bv = (k < kw) ? xs[s * LS_KS + k] : 0.f;
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = kk * 4 + r;
+          if (c < D_OUT && k < kw) a[c * D_IN + k0 + k] += sc * acc[r];
+        }
+      }
+    }
+    if (tid < D_OUT) {
+      float db = 0.f;
+      for (int s = 0; s < 16; ++s) db += G[s][tid];
+      a[D_OUT * D_IN + tid] += sc * db;
+    }
+    // 5. the step's noise, a -= lr (S C / Bq) xi_e; the last step's goes into the write below
+    if (noisy && e < E - 1) {
+      __syncthreads();   // the dW pass owns entries of a by lane, this pass by index
+      for (int i = tid; i < nparam; i += SM_THREADS) a[i] -= nsc * xi(i, e);
+    }
+    // (the next step's first barrier, or the one below, orders these writes of a before their readers)
+  }
+  __syncthreads();
+  // 6. delta = a_E (with the last step's noise), quantised like updateFloatToInt
+  long long* qd = qdelta + (size_t)p * nparam;
+  for (int i = tid; i < nparam; i += SM_THREADS) {
+    float v = a[i];
+    if (noisy) v -= nsc * xi(i, E - 1);
+    if (A_IN_LDS || noisy) dst[i] = v;
+    qd[i] = quantize(v, qscale);
+  }
+}
+}  // namespace
+
+// =====================================================================================
 // K1t: top-k sparsification of the step's rows, in place (the reference's theta, ML/code/linear_model.py:48-88).
 // Row p keeps its k entries of largest fp32 magnitude -- key(j) = bits(delta[j]) & 0x7fffffff, monotone as an
 // integer; ties at the k-th key are kept in ascending index order -- and every other entry becomes delta = 0.0f,
@@ -1987,6 +2181,44 @@ extern "C" int bsc_local_steps(int loss, const float* X, const int* y, const lon
                    : local_steps_launch<CrossEntropyLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN,
                                                           D_OUT, B, P, seed, iteration, max_norm, qscale, E, lr, delta,
                                                           qdelta, loss_out, lo, ones, nones);
+}
+
+namespace {
+template <class Loss>
+int dpsgd_steps_launch(hipStream_t s, int nparam, const float* X, const int* y, const long long* off, const int* ntrain,
+                       const int* pid, const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed,
+                       int iteration, double qscale, float clip, float sigma, int E, float lr, float* delta,
+                       long long* qdelta, float* loss, int lo, int* ones, int nones) {
+  if (nparam <= LS_LDS_A)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dpsgd_steps<Loss, true>), dim3(P), dim3(SM_THREADS),
+                       (size_t)nparam * sizeof(float), s, X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration,
+                       qscale, clip, sigma, E, lr, delta, qdelta, loss, lo, ones, nones);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dpsgd_steps<Loss, false>), dim3(P), dim3(SM_THREADS), 0, s, X, y, off, ntrain,
+                       pid, W, D_IN, D_OUT, B, P, seed, iteration, qscale, clip, sigma, E, lr, delta, qdelta, loss, lo,
+                       ones, nones);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+// K1p: E DP-SGD steps at rate lr under loss 0 (cross-entropy) or 1 (margin): per-example clip at `clip` (> 0), noise
+// multiplier `sigma` (>= 0; 0 draws nothing); K1e's arguments and limits otherwise, and its placement of a.
+extern "C" int bsc_dpsgd_steps(int loss, const float* X, const int* y, const long long* off, const int* ntrain,
+                               const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
+                               unsigned long long seed, int iteration, double qscale, float clip, float sigma, int E,
+                               float lr, float* delta, long long* qdelta, float* loss_out, int lo, int* ones, int nones,
+                               void* stream) {
+  if (D_IN <= 0 || D_OUT > 16 || B > 16 || E < 1 || E > LS_MAX_E || !(lr > 0.f) || !(clip > 0.f) || !(sigma >= 0.f) ||
+      loss < 0 || loss > 1)
+    return -1;
+  if (P <= 0) return 0;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  return loss == 1 ? dpsgd_steps_launch<MarginLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN, D_OUT,
+                                                    B, P, seed, iteration, qscale, clip, sigma, E, lr, delta, qdelta,
+                                                    loss_out, lo, ones, nones)
+                   : dpsgd_steps_launch<CrossEntropyLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN,
+                                                          D_OUT, B, P, seed, iteration, qscale, clip, sigma, E, lr,
+                                                          delta, qdelta, loss_out, lo, ones, nones);
 }
 
 // K1t on delta fp32 [P, D] / qdelta int64 [P, D] in place; kept (nullable) int32 [P].  k == D keeps everything:

@@ -55,6 +55,8 @@ struct TaskCfg {  // the softmax task's resident data and the pre-step's constan
   int topk = 0;   // entries each row of the step keeps (k_topk_rows behind the step); 0: all of them, no launch
   int local_E = 1;       // local SGD steps per round; above 1 the pre-step queues k_local_steps instead of the step
   float local_lr = 1.f;  // their rate
+  float dp_clip = 0.f;   // per-example clip C; above 0 the pre-step queues k_dpsgd_steps (local_E steps, may be 1)
+  float dp_sigma = 0.f;  // its noise multiplier S
   hipStream_t gram;
   const float* X;
   const int *y, *ntrain, *pid, *rows_arange;
@@ -506,6 +508,8 @@ extern "C" int bsc_round_bind_task(void* ctx, void* gram_stream, const float* X,
   t.topk = 0;
   t.local_E = 1;
   t.local_lr = 1.f;
+  t.dp_clip = 0.f;
+  t.dp_sigma = 0.f;
   t.bound = 1;
   return 0;
 }
@@ -536,6 +540,17 @@ extern "C" int bsc_round_task_local(void* ctx, int E, float lr) {
   if (c == nullptr || !c->task.bound || E < 1 || E > 64 || !(lr > 0.f)) return -1;
   c->task.local_E = E;
   c->task.local_lr = lr;
+  return 0;
+}
+
+// The bound task's DP-SGD step (clip = 0, the default of every bind: off; clip > 0: the pre-step queues k_dpsgd_steps in
+// place of the other steps, local_E steps at rate local_lr under the bound loss, each example's gradient clipped to
+// clip and N(0, (sigma clip)^2) added to the clipped sum).  Top-k still follows it.
+extern "C" int bsc_round_task_dpsgd(void* ctx, float clip, float sigma) {
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || !c->task.bound || !(clip >= 0.f) || !(sigma >= 0.f) || (sigma > 0.f && !(clip > 0.f))) return -1;
+  c->task.dp_clip = clip;
+  c->task.dp_sigma = sigma;
   return 0;
 }
 
@@ -619,7 +634,11 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
   RC_CHECK(hipEventRecord(c->ev_pre, c->main));
   RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
   if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
-  if (t.local_E > 1)
+  if (t.dp_clip > 0.f)
+    RC_CHECK(bsc_dpsgd_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.qs,
+                             t.dp_clip, t.dp_sigma, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss, t.lo, ones,
+                             c->spec_cap, gs));
+  else if (t.local_E > 1)
     RC_CHECK(bsc_local_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it,
                              t.max_norm, t.qs, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss, t.lo, ones,
                              c->spec_cap, gs));

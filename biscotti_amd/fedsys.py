@@ -31,6 +31,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="local SGD steps per worker and round, each on a fresh minibatch (k_local_steps; mnist and "
                          "lfw, 1..64, 1 = the single step)")
     ap.add_argument("--local-lr", type=float, default=1.0, metavar="ETA", help="the rate of those local steps (> 0)")
+    ap.add_argument("--dp-clip", type=float, default=0.0, metavar="C",
+                    help="DP-SGD local steps (k_dpsgd_steps; mnist and lfw): clip each example's gradient to L2 norm C "
+                         "before the minibatch is summed (0 = off)")
+    ap.add_argument("--dp-sigma", type=float, default=0.0, metavar="S",
+                    help="noise multiplier of those steps: N(0, (S C)^2) is added to the clipped sum (>= 0, needs --dp-clip)")
     return ap
 
 
@@ -54,7 +59,8 @@ def main(argv=None) -> int:
     from .protocol.fedsys import FedSysEngine
 
     comm = Comm.init(device=cfg.device)
-    eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr)
+    eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
+                       dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

@@ -26,7 +26,7 @@ class SoftmaxTask:
     def __init__(self, peers: range, num_peers: int, device, seed: int, poisoned: set[int] | None = None,
                  batch_size: int = 10, data_dir: str | None = None, federation: D.MnistFederation | None = None,
                  dims: tuple | None = None, loss: str = "ce", topk: float = 1.0, local_steps: int = 1,
-                 local_lr: float = 1.0):
+                 local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0):
         if loss not in ("ce", "margin"):
             raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
         if not 0.0 < topk <= 1.0:
@@ -41,6 +41,13 @@ class SoftmaxTask:
         # and sends the accumulated difference (K.local_steps); still a function of (W, peer, iteration).  1: the
         # single step and its own kernel, whatever local_lr
         self.local_steps, self.local_lr = int(local_steps), float(local_lr)
+        if not dp_clip >= 0 or not dp_sigma >= 0 or (dp_sigma > 0 and not dp_clip > 0):
+            raise ValueError(f"dp_clip is the per-example clip norm (>= 0, 0 = off) and dp_sigma its noise multiplier "
+                             f"(>= 0, needs dp_clip > 0), not dp_clip={dp_clip!r} dp_sigma={dp_sigma!r}")
+        # DP-SGD (docs/QUIRKS.md Q18): step() clips each example's gradient to dp_clip, adds N(0, (dp_sigma dp_clip)^2)
+        # to the clipped sum and divides by the batch (K.dpsgd_steps, for any local_steps); still a function of
+        # (W, peer, iteration).  0: off, today's branches
+        self.dp_clip, self.dp_sigma = float(dp_clip), float(dp_sigma)
         # "margin": the same linear scorer trained as SVMModel (svm_model.py under nn.MultiLabelMarginLoss with
         # the single target, client.py:28); evaluation, train_error and roni_rows are argmax-based: the same
         self.loss = loss
@@ -105,7 +112,11 @@ class SoftmaxTask:
             pid = h2d(peers, torch.int32, self.device)
             if len(self._sel_cache) < 64:
                 self._sel_cache[key] = pid
-        if self.local_steps > 1:
+        if self.dp_clip > 0:
+            delta, qdelta, loss = K.dpsgd_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
+                                                self.batch, self.seed, iteration, self.dp_clip, self.dp_sigma,
+                                                self.local_steps, self.local_lr, loss=self.loss, lo=self.peers[0])
+        elif self.local_steps > 1:
             delta, qdelta, loss = K.local_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
                                                 self.batch, self.seed, iteration, self.local_steps, self.local_lr,
                                                 loss=self.loss, lo=self.peers[0])
@@ -286,11 +297,13 @@ MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 
 def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax",
-              topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, **kw):
+              topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0,
+              dp_sigma: float = 0.0, **kw):
     """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
     loss="margin"); creditcard has its logistic model only.  topk < 1: mnist / lfw's peers send top-k sparsified
     updates (SoftmaxTask's topk).  local_steps > 1: they run that many local SGD steps per round at rate local_lr
-    (SoftmaxTask's local_steps)."""
+    (SoftmaxTask's local_steps).  dp_clip > 0: their steps are DP-SGD steps, per-example clip dp_clip and noise
+    multiplier dp_sigma (SoftmaxTask's dp_clip)."""
     if model not in MODELS:
         raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
     if model == "svm" and dataset == "creditcard":
@@ -299,10 +312,13 @@ def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, mod
         raise ValueError("topk < 1 needs mnist or lfw: creditcard adds its noise at the source, its updates are dense")
     if (local_steps != 1 or local_lr != 1.0) and dataset == "creditcard":
         raise ValueError("local_steps / local_lr need mnist or lfw: creditcard's logistic step is a single noisy step")
+    if (dp_clip != 0 or dp_sigma != 0) and dataset == "creditcard":
+        raise ValueError("dp_clip / dp_sigma need mnist or lfw: creditcard's logistic step already noises at the source")
     loss = "margin" if model == "svm" else "ce"
     kw["topk"] = topk
     if dataset != "creditcard":
         kw["local_steps"], kw["local_lr"] = local_steps, local_lr
+        kw["dp_clip"], kw["dp_sigma"] = dp_clip, dp_sigma
     if dataset == "mnist":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)

@@ -603,8 +603,11 @@ class NativeSecAgg:
             _check(hip().bsc_round_task_loss(self.ctx, 1), "round_task_loss")
         if getattr(task, "topk_k", 0):   # the pre-step queues k_topk_rows behind the step (a bind resets it to off)
             _check(hip().bsc_round_task_topk(self.ctx, task.topk_k), "round_task_topk")
-        if getattr(task, "local_steps", 1) > 1:   # the pre-step queues k_local_steps (a bind resets it to one step)
+        dp = getattr(task, "dp_clip", 0.0) > 0
+        if getattr(task, "local_steps", 1) > 1 or dp:   # k_local_steps (a bind resets it to one step); DP-SGD's E, lr
             _check(hip().bsc_round_task_local(self.ctx, task.local_steps, task.local_lr), "round_task_local")
+        if dp:   # the pre-step queues k_dpsgd_steps in place of the other steps (a bind resets it to off)
+            _check(hip().bsc_round_task_dpsgd(self.ctx, task.dp_clip, task.dp_sigma), "round_task_dpsgd")
 
         def ev():
             e = torch.cuda.Event()

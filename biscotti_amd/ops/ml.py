@@ -202,6 +202,69 @@ def local_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, E, l
                         seed, iteration, max_norm, qscale, lo, E=int(E), lr=float(lr))
 
 
+def dpsgd_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, clip, sigma=0.0, E=1, lr=1.0, loss="ce",
+                qscale=1e4, lo=-1):
+    """E DP-SGD steps per peer at rate lr under loss "ce" or "margin" (k_dpsgd_steps, docs/QUIRKS.md Q18): step e
+    takes local_steps' minibatch and scorer float32(W) + a_e, clips each example's gradient to L2 norm `clip` --
+    c_s = min(1, clip / (n_s + 1e-6)), n_s = ||gamma_s|| sqrt(||x_s||^2 + 1) for the rank-one gamma_s (x) (x_s, 1) --
+    sums the clipped gradients, adds sigma * clip * N(0, 1) per entry (Philox counter (j, iteration, peer,
+    0xD95D ^ (e << 16)); sigma = 0 draws nothing), divides by Bq and adds -lr times that to a.  There is no clip of
+    the mean gradient.  Returns (delta = a_E fp32 [P, nparam], qdelta int64, loss fp32 [P] of the last step); the
+    other arguments are softmax_step's."""
+    if loss not in ("ce", "margin"):
+        raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
+    if E != int(E) or not 1 <= E <= LOCAL_STEPS_MAX or not lr > 0:
+        raise ValueError(f"DP-SGD steps: an integer E in 1..{LOCAL_STEPS_MAX} and a rate lr > 0, not E={E!r} lr={lr!r}")
+    if not clip > 0 or not sigma >= 0:
+        raise ValueError(f"DP-SGD steps: a clip > 0 and a noise multiplier sigma >= 0, not clip={clip!r} sigma={sigma!r}")
+    E, lr, clip, sigma = int(E), float(lr), float(clip), float(sigma)
+    P = pid.numel()
+    nw = d_out * d_in
+    nparam = nw + d_out
+    dev = X.device
+    delta = torch.empty((P, nparam), dtype=torch.float32, device=dev)
+    qdelta = torch.empty((P, nparam), dtype=torch.int64, device=dev)
+    lossv = torch.empty((P,), dtype=torch.float32, device=dev)
+    if dev.type == "cuda":
+        assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+        assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
+        assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
+        _check(hip().bsc_dpsgd_steps(int(loss == "margin"), _p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in,
+                                     d_out, B, P, seed & (2**64 - 1), iteration, float(qscale), clip, sigma, E, lr,
+                                     _p(delta), _p(qdelta), _p(lossv), int(lo), None, 0, _stream()), "dpsgd_steps")
+        return delta, qdelta, lossv
+    loss_rows = _margin_rows if loss == "margin" else _ce_rows
+    Wm = W.to(torch.float32)
+    pids = pid.tolist()
+    if lo >= 0:
+        offs = [int(off[q - lo]) for q in pids]
+        ns = [int(ntrain[q - lo]) for q in pids]
+    else:
+        offs, ns = off.tolist(), ntrain.tolist()
+    for p in range(P):
+        a = torch.zeros(nparam)
+        Bq = max(min(B, ns[p]), 1)
+        for e in range(E):
+            idx = minibatch_indices(pids[p], iteration, ns[p], B, seed, tag=0x5EED ^ (e << 16))
+            rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
+            xb = (X[rows] - 0.5) / 0.5
+            w = Wm + a
+            logits = xb @ w[:nw].view(d_out, d_in).T + w[nw:]
+            last, g = loss_rows(logits, y[rows].long())       # g = gamma / Bq
+            n_s = Bq * torch.linalg.vector_norm(g, dim=1) * torch.sqrt((xb * xb).sum(1) + 1.0)
+            g = g * torch.clamp(clip / (n_s + 1e-6), max=1.0)[:, None]
+            a = a - lr * torch.cat([(g.T @ xb).reshape(-1), g.sum(0)])
+            if sigma > 0:
+                r = philox4x32(np.arange(nparam), iteration, pids[p], 0xD95D ^ (e << 16), seed & MASK32,
+                               (seed >> 32) & MASK32)
+                nsc = float(np.float32(lr) * (np.float32(sigma) * np.float32(clip) / np.float32(Bq)))
+                a = a - nsc * torch.from_numpy(_gauss(r[0], r[1]))
+        delta[p] = a
+        qdelta[p] = torch.from_numpy((a.double().numpy() * qscale).astype(np.int64))
+        lossv[p] = last
+    return delta, qdelta, lossv
+
+
 # ---------------------------------------------------------------------------- K1t top-k rows
 def topk_rows_(delta, qdelta, k: int, kept=None):
     """Top-k sparsification of the step's rows, in place: row p keeps its k entries of largest fp32 magnitude and

@@ -67,6 +67,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "difference (k_local_steps; mnist and lfw, 1..64, 1 = today's single step).  A chain does "
                          "not record it: --resume needs the same --local-steps and --local-lr")
     ap.add_argument("--local-lr", type=float, default=1.0, metavar="ETA", help="the rate of those local steps (> 0)")
+    ap.add_argument("--dp-clip", type=float, default=0.0, metavar="C",
+                    help="DP-SGD local steps (k_dpsgd_steps; mnist and lfw): clip each example's gradient to L2 norm C "
+                         "before the minibatch is summed (0 = off, today's steps).  A chain does not record it: "
+                         "--resume needs the same --dp-clip and --dp-sigma")
+    ap.add_argument("--dp-sigma", type=float, default=0.0, metavar="S",
+                    help="noise multiplier of those steps: N(0, (S C)^2) is added to the clipped sum (>= 0, needs --dp-clip)")
     return ap
 
 
@@ -95,7 +101,8 @@ def main(argv=None) -> int:
     from .protocol.engine import BiscottiEngine
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
-    eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr)
+    eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
+                         dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma)
     eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
@@ -167,7 +174,8 @@ def _rpc_peer_main(cfg, ns) -> int:
         addrs = [f"127.0.0.1:{8000 + i}" for i in range(cfg.num_nodes)]
     cfg = dataclasses.replace(cfg, device="cpu")
     peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0,
-                   model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr)
+                   model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
+                   dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma)
     try:
         import time
 

@@ -2,12 +2,14 @@
 functions and which torch / native calls hold the round's host thread.
 
     python scripts/prof_rounds.py [--warm 30] [--rounds 200] [--emulate-world N] [--device-sign] [--model svm]
-                                  [--topk THETA] [--local-steps E] [--local-lr ETA] [--no-profile] [-o out.txt]
+                                  [--topk THETA] [--local-steps E] [--local-lr ETA] [--dp-clip C] [--dp-sigma S]
+                                  [--no-profile] [-o out.txt]
 
 --emulate-world N profiles rank 0 of an N-rank job (bench.py --emulate-world: the collectives filled locally).
 --device-sign sets engine.sign_device (the verifiers' signatures from k_schnorr_sign).  --model svm runs the rounds
 with the margin-loss local step (k_margin_step) instead of k_softmax_step.  --topk THETA runs them with top-k sparsified updates (k_topk_rows behind the step).
 --local-steps E [--local-lr ETA] runs them with E local SGD steps per peer (k_local_steps instead of the step).
+--dp-clip C [--dp-sigma S] runs them with DP-SGD steps (k_dpsgd_steps instead of the step, for any --local-steps).
 --no-profile times the same rounds without cProfile.  The last line printed is one JSON summary: ms per round
 (wall), the round thread's CPU us per round, the final drain's parts and the signer's stats.
 """
@@ -28,7 +30,7 @@ from biscotti_amd.protocol.config import RunConfig  # noqa: E402
 from biscotti_amd.protocol.engine import BiscottiEngine  # noqa: E402
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--warm", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=200)
@@ -38,13 +40,20 @@ def main():
     ap.add_argument("--topk", type=float, default=1.0)
     ap.add_argument("--local-steps", type=int, default=1)
     ap.add_argument("--local-lr", type=float, default=1.0)
+    ap.add_argument("--dp-clip", type=float, default=0.0)
+    ap.add_argument("--dp-sigma", type=float, default=0.0)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("-o", "--out", default=None)
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     comm = Comm.emulated(a.emulate_world) if a.emulate_world > 1 else Comm.init()
     torch.set_num_threads(1)
     eng = BiscottiEngine(RunConfig(num_nodes=100, seed=0, max_iterations=10**9, host_threads=14, lazy_eval=True), comm,
-                         model=a.model, topk=a.topk, local_steps=a.local_steps, local_lr=a.local_lr)
+                         model=a.model, topk=a.topk, local_steps=a.local_steps, local_lr=a.local_lr,
+                         dp_clip=a.dp_clip, dp_sigma=a.dp_sigma)
     eng.sign_device = a.device_sign
     for _ in range(a.warm):
         eng.run_round()
@@ -71,6 +80,7 @@ def main():
                 f.write(txt)
         print(txt[:6000])
     summary = {"model": eng.model, "topk": eng.topk, "local_steps": eng.local_steps, "local_lr": eng.local_lr,
+               "dp_clip": eng.dp_clip, "dp_sigma": eng.dp_sigma,
                "device_sign": a.device_sign, "profiled": pr is not None,
                "rounds": a.rounds, "ms_per_round": 1e3 * (t1 - t0) / a.rounds, "host_thread_us_per_round": 1e6 * (c1 - c0) / a.rounds,
                "drain_parts_ms": getattr(eng, "drain_parts_ms", None),

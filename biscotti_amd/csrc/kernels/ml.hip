@@ -684,6 +684,258 @@ BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_dpsgd_steps(
 }  // namespace
 
 // =====================================================================================
+// K1l: E local steps on lots of up to LOT_MAX = 256 examples (--lot-size L; docs/QUIRKS.md Q19).  K1e's rule
+// (DP = false: clip of the mean at max_norm) or K1p's (DP = true: per-example clip, noise on the clipped sum) with
+// Lq = min(L, n) rows per step in place of Bq <= 16; draws, tags, scorer, noise counters and outputs are theirs.
+// One 256-thread workgroup per peer; the lot, not a 16-row MFMA tile, is the unit of a step:
+//   draw    per step (E * L indices do not fit), by wave 0.  The 64 lanes run Philox for 64 counters at once and
+//           reduce their 256 candidates mod n; the candidates are then taken in the reference's order, each broadcast
+//           and tested against the accepted indices -- held four per lane over the wave -- by four compares and one
+//           ballot, so the rejection rule yields minibatch_indices' exact sequence.  n <= L: the shard is taken whole
+//           in storage order (the draw's order only decides which rows share a tile; the sums do not depend on it)
+//   pass A  row tile by row tile: K1p's logits pass (LS_KT-wide tiles, f32 MFMA 16x16x4, B = (float)W + a formed in
+//           registers; under DP ||x_s||^2 by one FMA per k step), then Loss::row by one thread per row.  The lot's
+//           whole G [256][16] stays in LDS, under DP with c_s already folded into its rows
+//   pass B  K tile by K tile, the lot as the MFMA's K dimension: every row tile of the K tile is staged again (the
+//           rows are L2-hot) while a wave's four 16-column accumulators stay in registers, so dW[c][k] has MFMA depth
+//           Lq and is finished once, by the one lane that owns it.  DP: the finished entry takes its noise and -lr
+//           and goes straight into a (pass A is over: in place is safe; there is no gradient buffer).  Else it goes
+//           into the step gradient g and its square into the lane's share of ||g||^2 (fp64; lanes, then waves, in a
+//           fixed order); once the norm is known a last pass does a -= lr c g
+//   a, g    in LDS when nparam <= LS_LDS_A (g behind a), else a is the peer's delta row and g its row of the
+//           launcher's [P, nparam] workspace
+// LDS: 17664 B tile + 4 KiB of per-wave logits + 16 KiB G + 1 KiB of indices + 64 B of losses + 256 B of row norms
+// (DP) or 32 B of norm partials (not DP) = 39488 / 39264 B static, plus a (DP: at most 32 KiB) or a and g (at most
+// 64 KiB) dynamic: up to 70.6 KiB under DP and 102.3 KiB without, above the default 64 KiB and inside gfx950's
+// 160 KiB per workgroup (one workgroup per CU; a round launches one per peer).  The launcher raises the dynamic
+// limit of the two A_IN_LDS instances once, with hipFuncSetAttribute, and returns its error if that fails.
+// No atomics, no reduction whose order depends on timing: two runs give the same bytes.
+// =====================================================================================
+constexpr int LOT_MAX = 256;
+
+namespace {
+template <class Loss, bool A_IN_LDS, bool DP>
+BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_lot_steps(
+    const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
+    int D_OUT, int L, int P, unsigned long long seed, int iteration, float max_norm, double qscale, float clip,
+    float sigma, int E, float lr, float* delta, long long* qdelta, float* loss, float* gwork, int lo, int* ones,
+    int nones) {
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  if (ones != nullptr && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < nones; i += blockDim.x) ones[i] = 1;
+  extern __shared__ float lot_ag[];       // A_IN_LDS: a [nparam], then (not DP) g [nparam]; else unused (0 bytes)
+  __shared__ float xs[16 * LS_KS];        // one K tile of one row tile, transformed; rows >= Lq are zero
+  __shared__ float red[4][16][16];        // per-wave partial logits [s][c] of the row tile
+  __shared__ float rsq[4][16];            // per-wave partial ||x_s||^2 (DP)
+  __shared__ float G[LOT_MAX][16];        // the lot's (c_s) d(mean loss) / d(logits); rows >= Lq of the last tile: 0
+  __shared__ int idx[LOT_MAX];            // this step's lot
+  __shared__ float rl[16];                // the row threads' loss sums
+  __shared__ double nrm[SM_THREADS / 64];
+  const int p = blockIdx.x;
+  if (p >= P) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nw = D_OUT * D_IN, nparam = nw + D_OUT;
+  const uint32_t peer = (uint32_t)pid[p];
+  const int li = lo >= 0 ? pid[p] - lo : p;
+  const long long offp = off[li];
+  const int n = ntrain[li];
+  const int Lq = min(L, n);
+  const int rtiles = (Lq + 15) / 16;
+  float* dst = delta + (size_t)p * nparam;
+  float* a = A_IN_LDS ? lot_ag : dst;
+  float* g = DP ? nullptr : A_IN_LDS ? lot_ag + nparam : gwork + (size_t)p * nparam;
+  const uint32_t k0s = (uint32_t)seed, k1s = (uint32_t)(seed >> 32);
+  for (int i = tid; i < nparam; i += SM_THREADS) a[i] = 0.f;
+  const int ktiles = (D_IN + LS_KT - 1) / LS_KT;
+  const int row = lane & 15, kk = lane >> 4;   // MFMA operand coordinates of this lane
+  const bool noisy = DP && sigma > 0.f;        // uniform
+  const float nsc = lr * (sigma * clip / (float)max(Lq, 1));   // what one N(0, 1) draw moves an entry of a by
+  auto xi = [&](int j, int e) __attribute__((always_inline)) {
+    const u4 r = philox(u4{(uint32_t)j, (uint32_t)iteration, peer, 0xD95Du ^ ((uint32_t)e << 16)}, k0s, k1s);
+    return gauss(r.x, r.y);
+  };
+  auto stage = [&](int rt, int kt) __attribute__((always_inline)) {  // (x - 0.5) / 0.5; zero padding
+    const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+    for (int i = tid; i < 16 * kw; i += SM_THREADS) {
+      const int sl = i / kw, k = i % kw, s = rt * 16 + sl;
+      float v = 0.f;
+      if (s < Lq) v = (X[(offp + idx[s]) * (long long)D_IN + k0 + k] - 0.5f) * 2.0f;
+      xs[sl * LS_KS + k] = v;
+    }
+  };
+  for (int e = 0; e < E; ++e) {
+    __syncthreads();   // the last step's readers of idx and writers of a are done
+    // 1. the step's lot: minibatch_indices(peer, iteration, n, L, seed, tag) by wave 0
+    if (wid == 0) {
+      if (n <= L) {
+        for (int i = lane; i < Lq; i += 64) idx[i] = i;
+      } else {
+        const uint32_t tag = 0x5EEDu ^ ((uint32_t)e << 16);
+        int h0 = -1, h1 = -1, h2 = -1, h3 = -1;   // accepted index j lives in lane j & 63, register j >> 6
+        int cnt = 0;
+        for (uint32_t ctr = 0; cnt < Lq; ctr += 64) {
+          const u4 r = philox(u4{peer, (uint32_t)iteration, ctr + (uint32_t)lane, tag}, k0s, k1s);
+          const int c0 = (int)(r.x % (uint32_t)n), c1 = (int)(r.y % (uint32_t)n), c2 = (int)(r.z % (uint32_t)n),
+                    c3 = (int)(r.w % (uint32_t)n);
+          for (int sl = 0; sl < 64 && cnt < Lq; ++sl) {
+            const int q4[4] = {__shfl(c0, sl), __shfl(c1, sl), __shfl(c2, sl), __shfl(c3, sl)};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int c = q4[q];
+              const bool dup = (h0 == c) | (h1 == c) | (h2 == c) | (h3 == c);
+              if (cnt < Lq && __ballot(dup) == 0ull) {   // uniform: cnt and the ballot are the same in every lane
+                if (lane == (cnt & 63)) {
+                  const int w = cnt >> 6;
+                  h0 = w == 0 ? c : h0;
+                  h1 = w == 1 ? c : h1;
+                  h2 = w == 2 ? c : h2;
+                  h3 = w == 3 ? c : h3;
+                  idx[cnt] = c;
+                }
+                ++cnt;
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // 2. pass A: per row tile the logits of w_e = (float)W + a (and the rows' squared norms), then the loss and G
+    float lsum = 0.f;
+    for (int rt = 0; rt < rtiles; ++rt) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      float xx = 0.f;   // this lane's share of ||x_row||^2
+      for (int kt = 0; kt < ktiles; ++kt) {
+        const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+        __syncthreads();  // the tile's last readers are done
+        stage(rt, kt);
+        __syncthreads();
+        const int ksteps = (kw + 3) / 4;
+        const int per = (ksteps + 3) / 4;
+        for (int st = wid * per; st < min(ksteps, (wid + 1) * per); ++st) {
+          const int k = st * 4 + kk;
+          const bool in = k < kw;
+          const float av = in ? xs[row * LS_KS + k] : 0.f;
+          float bv = 0.f;
+          if (in && row < D_OUT) bv = (float)W[row * D_IN + k0 + k] + a[row * D_IN + k0 + k];
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+          if (DP) xx = fmaf(av, av, xx);
+        }
+      }
+      if (DP) {
+        xx += __shfl_xor(xx, 16);
+        xx += __shfl_xor(xx, 32);
+        if (kk == 0) rsq[wid][row] = xx;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wid][kk * 4 + r][row] = acc[r];
+      __syncthreads();
+      // one thread per row of the tile; red and rsq are next written behind the next tile's staging barriers
+      if (tid < 16) {
+        const int s = rt * 16 + tid;
+        if (s < Lq) {
+          float* lg = red[0][tid];   // the row's logits, summed in place (LDS: the label indexes them)
+          for (int c = 0; c < D_OUT; ++c)
+            lg[c] = red[0][tid][c] + red[1][tid][c] + red[2][tid][c] + red[3][tid][c] +
+                    ((float)W[nw + c] + a[nw + c]);
+          lsum += Loss::row(lg, D_OUT, y[offp + idx[s]], Lq, G[s]);
+          if (DP) {
+            float gg = 0.f;
+            for (int c = 0; c < D_OUT; ++c) gg = fmaf(G[s][c], G[s][c], gg);
+            const float x2 = (rsq[0][tid] + rsq[1][tid]) + (rsq[2][tid] + rsq[3][tid]);
+            const float ns = (float)Lq * sqrtf(gg) * sqrtf(x2 + 1.f);   // ||gamma_s (x) (x_s, 1)||, gamma_s = Lq G_s
+            const float coef = clip / (ns + 1e-6f);
+            if (coef < 1.f)
+              for (int c = 0; c < D_OUT; ++c) G[s][c] *= coef;
+          }
+          for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
+        } else {
+          for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
+        }
+      }
+    }
+    if (tid < 16) rl[tid] = lsum;
+    __syncthreads();   // G is complete
+    if (tid == 0 && e == E - 1) {
+      float l = 0.f;
+      for (int s = 0; s < 16; ++s) l += rl[s];
+      loss[p] = l / (float)max(Lq, 1);
+    }
+    // 3. pass B: dW[c][k] = sum_{s < Lq} G[s][c] xs[s][k], K tile by K tile; wave w owns column tiles w, w + 4, ...
+    double sq = 0.0;   // this lane's share of ||g||^2 (not DP)
+    auto finish = [&](int i, float v) __attribute__((always_inline)) {
+      if (DP) {
+        float u = a[i] - lr * v;
+        if (noisy) u -= nsc * xi(i, e);
+        a[i] = u;
+      } else {
+        g[i] = v;
+        sq += (double)v * (double)v;
+      }
+    };
+    for (int kt = 0; kt < ktiles; ++kt) {
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      const int ntiles = (kw + 15) / 16;
+      f32x4 acc[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int rt = 0; rt < rtiles; ++rt) {
+        __syncthreads();
+        stage(rt, kt);
+        __syncthreads();
+        float av[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) av[ks] = G[rt * 16 + ks * 4 + kk][row];   // A[c = row][s]
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = (wid + 4 * j) * 16 + row;
+          if (wid + 4 * j < ntiles) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+              const float bv = (k < kw) ? xs[(ks * 4 + kk) * LS_KS + k] : 0.f;
+              acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ks], bv, acc[j], 0, 0, 0);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = (wid + 4 * j) * 16 + row;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = kk * 4 + r;
+          if (c < D_OUT && k < kw) finish(c * D_IN + k0 + k, acc[j][r]);
+        }
+      }
+    }
+    if (tid < D_OUT) {
+      float db = 0.f;
+      for (int s = 0; s < rtiles * 16; ++s) db += G[s][tid];
+      finish(nw + tid, db);
+    }
+    // 4. not DP: the clip of the mean from ||g||, then a -= lr c g
+    if (!DP) {
+      for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+      if (lane == 0) nrm[wid] = sq;
+      __syncthreads();   // also: pass B owns entries of g by lane, this pass by index
+      const float tot = (float)sqrt((nrm[0] + nrm[1]) + (nrm[2] + nrm[3]));
+      const float coef = max_norm / (tot + 1e-6f);
+      const float sc = -(lr * (coef < 1.f ? coef : 1.f));
+      for (int i = tid; i < nparam; i += SM_THREADS) a[i] += sc * g[i];
+    }
+  }
+  __syncthreads();
+  // 5. delta = a_E, quantised like updateFloatToInt
+  long long* qd = qdelta + (size_t)p * nparam;
+  for (int i = tid; i < nparam; i += SM_THREADS) {
+    const float v = a[i];
+    if (A_IN_LDS) dst[i] = v;
+    qd[i] = quantize(v, qscale);
+  }
+}
+}  // namespace
+
+// =====================================================================================
 // K1t: top-k sparsification of the step's rows, in place (the reference's theta, ML/code/linear_model.py:48-88).
 // Row p keeps its k entries of largest fp32 magnitude -- key(j) = bits(delta[j]) & 0x7fffffff, monotone as an
 // integer; ties at the k-th key are kept in ascending index order -- and every other entry becomes delta = 0.0f,
@@ -2219,6 +2471,56 @@ extern "C" int bsc_dpsgd_steps(int loss, const float* X, const int* y, const lon
                    : dpsgd_steps_launch<CrossEntropyLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN,
                                                           D_OUT, B, P, seed, iteration, qscale, clip, sigma, E, lr,
                                                           delta, qdelta, loss_out, lo, ones, nones);
+}
+
+namespace {
+template <class Loss, bool DP>
+int lot_steps_launch(hipStream_t s, int nparam, const float* X, const int* y, const long long* off, const int* ntrain,
+                     const int* pid, const double* W, int D_IN, int D_OUT, int L, int P, unsigned long long seed,
+                     int iteration, float max_norm, double qscale, float clip, float sigma, int E, float lr,
+                     float* delta, long long* qdelta, float* loss, float* gwork, int lo, int* ones, int nones) {
+  if (nparam <= LS_LDS_A) {
+    // static + dynamic LDS passes the default 64 KiB (K1l's header): opt in once per instance, up to a (and g) at LS_LDS_A
+    static const hipError_t optin =
+        hipFuncSetAttribute((const void*)k_lot_steps<Loss, true, DP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (DP ? 1 : 2) * LS_LDS_A * (int)sizeof(float));
+    if (optin != hipSuccess) return (int)optin;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lot_steps<Loss, true, DP>), dim3(P), dim3(SM_THREADS),
+                       (size_t)(DP ? 1 : 2) * nparam * sizeof(float), s, X, y, off, ntrain, pid, W, D_IN, D_OUT, L, P,
+                       seed, iteration, max_norm, qscale, clip, sigma, E, lr, delta, qdelta, loss, gwork, lo, ones,
+                       nones);
+  } else {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lot_steps<Loss, false, DP>), dim3(P), dim3(SM_THREADS), 0, s, X, y, off,
+                       ntrain, pid, W, D_IN, D_OUT, L, P, seed, iteration, max_norm, qscale, clip, sigma, E, lr, delta,
+                       qdelta, loss, gwork, lo, ones, nones);
+  }
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+// K1l: E local steps on lots of L <= LOT_MAX examples under loss 0 (cross-entropy) or 1 (margin).  clip == 0: K1e's
+// rule (the mean gradient clipped at max_norm); clip > 0: K1p's (per-example clip, noise multiplier sigma >= 0, and
+// max_norm unused).  gwork: fp32 [P, nparam] step-gradient workspace, needed when clip == 0 and nparam > LS_LDS_A
+// (else nullable, untouched).  The other arguments and limits are K1e's.
+extern "C" int bsc_lot_steps(int loss, const float* X, const int* y, const long long* off, const int* ntrain,
+                             const int* pid, const double* W, int D_IN, int D_OUT, int L, int P,
+                             unsigned long long seed, int iteration, float max_norm, double qscale, float clip,
+                             float sigma, int E, float lr, float* delta, long long* qdelta, float* loss_out,
+                             float* gwork, int lo, int* ones, int nones, void* stream) {
+  if (D_IN <= 0 || D_OUT > 16 || L < 1 || L > LOT_MAX || E < 1 || E > LS_MAX_E || !(lr > 0.f) || !(clip >= 0.f) ||
+      !(sigma >= 0.f) || (sigma > 0.f && !(clip > 0.f)) || loss < 0 || loss > 1)
+    return -1;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  const bool dp = clip > 0.f;
+  if (!dp && nparam > LS_LDS_A && gwork == nullptr) return -1;
+  if (P <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+#define BSC_LOT_LAUNCH(LOSS, DPV)                                                                                     \
+  lot_steps_launch<LOSS, DPV>(s, nparam, X, y, off, ntrain, pid, W, D_IN, D_OUT, L, P, seed, iteration, max_norm,     \
+                              qscale, clip, sigma, E, lr, delta, qdelta, loss_out, gwork, lo, ones, nones)
+  if (loss == 1) return dp ? BSC_LOT_LAUNCH(MarginLoss, true) : BSC_LOT_LAUNCH(MarginLoss, false);
+  return dp ? BSC_LOT_LAUNCH(CrossEntropyLoss, true) : BSC_LOT_LAUNCH(CrossEntropyLoss, false);
+#undef BSC_LOT_LAUNCH
 }
 
 // K1t on delta fp32 [P, D] / qdelta int64 [P, D] in place; kept (nullable) int32 [P].  k == D keeps everything:

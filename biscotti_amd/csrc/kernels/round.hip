@@ -57,6 +57,8 @@ struct TaskCfg {  // the softmax task's resident data and the pre-step's constan
   float local_lr = 1.f;  // their rate
   float dp_clip = 0.f;   // per-example clip C; above 0 the pre-step queues k_dpsgd_steps (local_E steps, may be 1)
   float dp_sigma = 0.f;  // its noise multiplier S
+  int lot = 0;           // examples per local step (--lot-size); above 0 the pre-step queues k_lot_steps for every step
+  float* lot_g = nullptr;   // its [P, nparam] step-gradient workspace (caller-owned; see bsc_lot_steps)
   hipStream_t gram;
   const float* X;
   const int *y, *ntrain, *pid, *rows_arange;
@@ -510,6 +512,8 @@ extern "C" int bsc_round_bind_task(void* ctx, void* gram_stream, const float* X,
   t.local_lr = 1.f;
   t.dp_clip = 0.f;
   t.dp_sigma = 0.f;
+  t.lot = 0;
+  t.lot_g = nullptr;
   t.bound = 1;
   return 0;
 }
@@ -551,6 +555,17 @@ extern "C" int bsc_round_task_dpsgd(void* ctx, float clip, float sigma) {
   if (c == nullptr || !c->task.bound || !(clip >= 0.f) || !(sigma >= 0.f) || (sigma > 0.f && !(clip > 0.f))) return -1;
   c->task.dp_clip = clip;
   c->task.dp_sigma = sigma;
+  return 0;
+}
+
+// The bound task's lot (L = 0, the default of every bind: off; L in 1..256: the pre-step queues k_lot_steps in place of
+// the other three steps -- local_E steps at rate local_lr on lots of L examples, DP-SGD's rule when dp_clip > 0, else
+// the clip of the mean).  gwork: the caller's fp32 [P, nparam] workspace for bsc_lot_steps (nullable where that is).
+extern "C" int bsc_round_task_lot(void* ctx, int L, float* gwork) {
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || !c->task.bound || L < 0 || L > 256) return -1;
+  c->task.lot = L;
+  c->task.lot_g = gwork;
   return 0;
 }
 
@@ -634,7 +649,11 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
   RC_CHECK(hipEventRecord(c->ev_pre, c->main));
   RC_CHECK(hipStreamWaitEvent(gs, c->ev_pre, 0));
   if (ones_wait != nullptr) RC_CHECK(hipStreamWaitEvent(gs, ones_wait, 0));
-  if (t.dp_clip > 0.f)
+  if (t.lot > 0)
+    RC_CHECK(bsc_lot_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.lot, t.P, t.seed, it,
+                           t.max_norm, t.qs, t.dp_clip, t.dp_sigma, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss,
+                           t.lot_g, t.lo, ones, c->spec_cap, gs));
+  else if (t.dp_clip > 0.f)
     RC_CHECK(bsc_dpsgd_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.qs,
                              t.dp_clip, t.dp_sigma, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss, t.lo, ones,
                              c->spec_cap, gs));

@@ -36,6 +36,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "before the minibatch is summed (0 = off)")
     ap.add_argument("--dp-sigma", type=float, default=0.0, metavar="S",
                     help="noise multiplier of those steps: N(0, (S C)^2) is added to the clipped sum (>= 0, needs --dp-clip)")
+    ap.add_argument("--lot-size", type=int, default=0, metavar="L",
+                    help="examples each local step draws, up to 256, in place of the batch size (k_lot_steps; mnist and "
+                         "lfw, 0 = off)")
     return ap
 
 
@@ -60,7 +63,7 @@ def main(argv=None) -> int:
 
     comm = Comm.init(device=cfg.device)
     eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
-                       dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma)
+                       dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

@@ -26,7 +26,7 @@ class SoftmaxTask:
     def __init__(self, peers: range, num_peers: int, device, seed: int, poisoned: set[int] | None = None,
                  batch_size: int = 10, data_dir: str | None = None, federation: D.MnistFederation | None = None,
                  dims: tuple | None = None, loss: str = "ce", topk: float = 1.0, local_steps: int = 1,
-                 local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0):
+                 local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0, lot_size: int = 0):
         if loss not in ("ce", "margin"):
             raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
         if not 0.0 < topk <= 1.0:
@@ -48,6 +48,13 @@ class SoftmaxTask:
         # to the clipped sum and divides by the batch (K.dpsgd_steps, for any local_steps); still a function of
         # (W, peer, iteration).  0: off, today's branches
         self.dp_clip, self.dp_sigma = float(dp_clip), float(dp_sigma)
+        if isinstance(lot_size, bool) or lot_size != int(lot_size) or not 0 <= lot_size <= K.LOT_MAX:
+            raise ValueError(f"lot_size is the number of examples a local step draws, an integer in 0..{K.LOT_MAX} "
+                             f"(0 = off: batch_size examples), not {lot_size!r}")
+        # lots (docs/QUIRKS.md Q19): every local step draws lot_size examples instead of batch_size and takes the rule
+        # above that is on -- DP-SGD's, else the local steps' -- through K.lot_steps (any local_steps / local_lr).
+        # batch_size keeps sizing the noisers' scale and RONI's rows.  0: off, today's branches
+        self.lot_size = int(lot_size)
         # "margin": the same linear scorer trained as SVMModel (svm_model.py under nn.MultiLabelMarginLoss with
         # the single target, client.py:28); evaluation, train_error and roni_rows are argmax-based: the same
         self.loss = loss
@@ -112,7 +119,12 @@ class SoftmaxTask:
             pid = h2d(peers, torch.int32, self.device)
             if len(self._sel_cache) < 64:
                 self._sel_cache[key] = pid
-        if self.dp_clip > 0:
+        if self.lot_size > 0:
+            delta, qdelta, loss = K.lot_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
+                                              self.lot_size, self.seed, iteration, self.local_steps, self.local_lr,
+                                              loss=self.loss, clip=self.dp_clip, sigma=self.dp_sigma,
+                                              lo=self.peers[0])
+        elif self.dp_clip > 0:
             delta, qdelta, loss = K.dpsgd_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
                                                 self.batch, self.seed, iteration, self.dp_clip, self.dp_sigma,
                                                 self.local_steps, self.local_lr, loss=self.loss, lo=self.peers[0])
@@ -298,12 +310,13 @@ MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax",
               topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0,
-              dp_sigma: float = 0.0, **kw):
+              dp_sigma: float = 0.0, lot_size: int = 0, **kw):
     """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
     loss="margin"); creditcard has its logistic model only.  topk < 1: mnist / lfw's peers send top-k sparsified
     updates (SoftmaxTask's topk).  local_steps > 1: they run that many local SGD steps per round at rate local_lr
     (SoftmaxTask's local_steps).  dp_clip > 0: their steps are DP-SGD steps, per-example clip dp_clip and noise
-    multiplier dp_sigma (SoftmaxTask's dp_clip)."""
+    multiplier dp_sigma (SoftmaxTask's dp_clip).  lot_size > 0: every step draws lot_size examples, up to 256, in
+    place of batch_size (SoftmaxTask's lot_size)."""
     if model not in MODELS:
         raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
     if model == "svm" and dataset == "creditcard":
@@ -314,11 +327,14 @@ def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, mod
         raise ValueError("local_steps / local_lr need mnist or lfw: creditcard's logistic step is a single noisy step")
     if (dp_clip != 0 or dp_sigma != 0) and dataset == "creditcard":
         raise ValueError("dp_clip / dp_sigma need mnist or lfw: creditcard's logistic step already noises at the source")
+    if lot_size != 0 and dataset == "creditcard":
+        raise ValueError("lot_size needs mnist or lfw: creditcard's logistic step draws batch_size examples")
     loss = "margin" if model == "svm" else "ce"
     kw["topk"] = topk
     if dataset != "creditcard":
         kw["local_steps"], kw["local_lr"] = local_steps, local_lr
         kw["dp_clip"], kw["dp_sigma"] = dp_clip, dp_sigma
+        kw["lot_size"] = lot_size
     if dataset == "mnist":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)

@@ -58,6 +58,7 @@ SIGNATURES = {
     "bsc_margin_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, P, P, P, I, P, I, P],
     "bsc_local_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, I, F, P, P, P, I, P, I, P],
     "bsc_dpsgd_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, D, F, F, I, F, P, P, P, I, P, I, P],
+    "bsc_lot_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, F, F, I, F, P, P, P, P, I, P, I, P],
     "bsc_topk_rows": [P, P, I, I, I, P, P],
     "bsc_logreg_step": [P, P, P, P, P, P, I, I, I, U64, P, D, D, P, D, P, P, P],
     "bsc_dp_noise": [P, I, I, P, I, P, U64, I, P, P],
@@ -95,6 +96,7 @@ SIGNATURES = {
     "bsc_round_task_topk": [P, I],
     "bsc_round_task_local": [P, I, F],
     "bsc_round_task_dpsgd": [P, F, F],
+    "bsc_round_task_lot": [P, I, P],
     "bsc_round_add_pre_slot": [P, P, P, P, P, P, P, P, P, P, P, P, P],
     "bsc_round_prestep_slot": [P, P, I, I],
     "bsc_round_set_nn_table": [P, P],

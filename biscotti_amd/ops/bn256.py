@@ -604,10 +604,15 @@ class NativeSecAgg:
         if getattr(task, "topk_k", 0):   # the pre-step queues k_topk_rows behind the step (a bind resets it to off)
             _check(hip().bsc_round_task_topk(self.ctx, task.topk_k), "round_task_topk")
         dp = getattr(task, "dp_clip", 0.0) > 0
-        if getattr(task, "local_steps", 1) > 1 or dp:   # k_local_steps (a bind resets it to one step); DP-SGD's E, lr
-            _check(hip().bsc_round_task_local(self.ctx, task.local_steps, task.local_lr), "round_task_local")
+        lot = getattr(task, "lot_size", 0)
+        if getattr(task, "local_steps", 1) > 1 or dp or lot:   # k_local_steps (a bind resets it to one step); DP-SGD's
+            _check(hip().bsc_round_task_local(self.ctx, task.local_steps, task.local_lr), "round_task_local")   # and the lot's E, lr
         if dp:   # the pre-step queues k_dpsgd_steps in place of the other steps (a bind resets it to off)
             _check(hip().bsc_round_task_dpsgd(self.ctx, task.dp_clip, task.dp_sigma), "round_task_dpsgd")
+        if lot:  # the pre-step queues k_lot_steps in place of the other three (a bind resets it to off)
+            from . import ml as K
+            self.lot_g = K.lot_workspace(P, d, getattr(task, "dp_clip", 0.0), dev)   # the steps of one stream share it
+            _check(hip().bsc_round_task_lot(self.ctx, lot, _ptr(self.lot_g)), "round_task_lot")
 
         def ev():
             e = torch.cuda.Event()

@@ -265,6 +265,55 @@ def dpsgd_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, clip
     return delta, qdelta, lossv
 
 
+LOT_MAX = 256   # k_lot_steps' LOT_MAX
+
+
+def lot_steps(X, y, off, ntrain, pid, W, d_in, d_out, L, seed, iteration, E=1, lr=1.0, loss="ce", clip=0.0, sigma=0.0,
+              max_norm=100.0, qscale=1e4, lo=-1):
+    """E local steps per peer on lots of L <= LOT_MAX examples (k_lot_steps, docs/QUIRKS.md Q19): step e draws
+    min(L, n) rows by minibatch_indices(pid, iteration, n, L, seed, tag=0x5EED ^ (e << 16)) and takes local_steps'
+    rule with B = L (clip == 0: the mean gradient clipped at max_norm) or dpsgd_steps' (clip > 0: per-example clip,
+    noise multiplier sigma, no clip of the mean).  Returns (delta = a_E fp32 [P, nparam], qdelta int64, loss fp32 [P]
+    of the last step); the other arguments are softmax_step's."""
+    if loss not in ("ce", "margin"):
+        raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
+    if isinstance(L, bool) or L != int(L) or not 1 <= L <= LOT_MAX:
+        raise ValueError(f"lot steps: an integer lot L in 1..{LOT_MAX}, not L={L!r}")
+    if E != int(E) or not 1 <= E <= LOCAL_STEPS_MAX or not lr > 0:
+        raise ValueError(f"lot steps: an integer E in 1..{LOCAL_STEPS_MAX} and a rate lr > 0, not E={E!r} lr={lr!r}")
+    if not clip >= 0 or not sigma >= 0 or (sigma > 0 and not clip > 0):
+        raise ValueError(f"lot steps: a clip >= 0 (0: the mean's clip) and a noise multiplier sigma >= 0 that needs a "
+                         f"clip, not clip={clip!r} sigma={sigma!r}")
+    L, E, lr, clip, sigma = int(L), int(E), float(lr), float(clip), float(sigma)
+    if X.device.type != "cuda":   # the CPU branches of the two rules take any B
+        if clip > 0:
+            return dpsgd_steps(X, y, off, ntrain, pid, W, d_in, d_out, L, seed, iteration, clip, sigma, E, lr, loss=loss,
+                               qscale=qscale, lo=lo)
+        return local_steps(X, y, off, ntrain, pid, W, d_in, d_out, L, seed, iteration, E, lr, loss=loss,
+                           max_norm=max_norm, qscale=qscale, lo=lo)
+    P = pid.numel()
+    nparam = d_out * d_in + d_out
+    assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+    assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
+    assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
+    delta = torch.empty((P, nparam), dtype=torch.float32, device=X.device)
+    qdelta = torch.empty((P, nparam), dtype=torch.int64, device=X.device)
+    lossv = torch.empty((P,), dtype=torch.float32, device=X.device)
+    gwork = lot_workspace(P, nparam, clip, X.device)
+    _check(hip().bsc_lot_steps(int(loss == "margin"), _p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, d_out, L,
+                               P, seed & (2**64 - 1), iteration, float(max_norm), float(qscale), clip, sigma, E, lr,
+                               _p(delta), _p(qdelta), _p(lossv), _p(gwork), int(lo), None, 0, _stream()), "lot_steps")
+    return delta, qdelta, lossv
+
+
+def lot_workspace(P: int, nparam: int, clip: float, device):
+    """bsc_lot_steps' step-gradient workspace: fp32 [P, nparam] where the update does not live in LDS (LS_LDS_A = 8192
+    parameters) and the rule is the mean's clip; None where the kernel needs none."""
+    if clip > 0 or nparam <= 8192:
+        return None
+    return torch.empty((P, nparam), dtype=torch.float32, device=device)
+
+
 # ---------------------------------------------------------------------------- K1t top-k rows
 def topk_rows_(delta, qdelta, k: int, kept=None):
     """Top-k sparsification of the step's rows, in place: row p keeps its k entries of largest fp32 magnitude and

@@ -73,6 +73,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "--resume needs the same --dp-clip and --dp-sigma")
     ap.add_argument("--dp-sigma", type=float, default=0.0, metavar="S",
                     help="noise multiplier of those steps: N(0, (S C)^2) is added to the clipped sum (>= 0, needs --dp-clip)")
+    ap.add_argument("--lot-size", type=int, default=0, metavar="L",
+                    help="examples each local step draws, up to 256, in place of the batch size (k_lot_steps; mnist and "
+                         "lfw, 0 = off, today's steps; the batch size keeps sizing the noisers' scale and RONI).  A "
+                         "chain does not record it: --resume needs the same --lot-size")
     return ap
 
 
@@ -102,7 +106,7 @@ def main(argv=None) -> int:
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
     eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
-                         dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma)
+                         dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size)
     eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
@@ -175,7 +179,7 @@ def _rpc_peer_main(cfg, ns) -> int:
     cfg = dataclasses.replace(cfg, device="cpu")
     peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0,
                    model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
-                   dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma)
+                   dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size)
     try:
         import time
 

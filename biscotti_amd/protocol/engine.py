@@ -79,7 +79,8 @@ class RoundResult:
 class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, VrfAuditMixin, SigAuditMixin,
                      FaultsMixin):
     def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0,
-                 local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0):
+                 local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0,
+                 lot_size: int = 0):
         cfg.validate()
         self.cfg = cfg
         # the ledger's model ("softmax", or "svm": the same scorer under the margin loss; models.make_task).  An
@@ -95,6 +96,9 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         # DP-SGD steps (models.make_task): the per-example clip and its noise multiplier; 0: off.  Engine arguments
         # like local_steps, and like it not recorded by a chain
         self.dp_clip, self.dp_sigma = dp_clip, dp_sigma
+        # lots (models.make_task): examples per local step, up to 256; 0: off, batch_size of them.  An engine argument
+        # like local_steps, and like it not recorded by a chain
+        self.lot_size = lot_size
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -136,7 +140,7 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         self.colluders = colluders
         self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk,
                               local_steps=local_steps, local_lr=local_lr, dp_clip=dp_clip, dp_sigma=dp_sigma,
-                              poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
+                              lot_size=lot_size, poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
                               epsilon=cfg.epsilon, colluders=colluders)
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
         # ---- ledger / protocol state

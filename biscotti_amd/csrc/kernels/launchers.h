@@ -53,6 +53,11 @@ int bsc_lot_steps(int loss, const float* X, const int* y, const long long* off, 
                   const double* W, int D_IN, int D_OUT, int L, int P, unsigned long long seed, int iteration,
                   float max_norm, double qscale, float clip, float sigma, int E, float lr, float* delta,
                   long long* qdelta, float* loss_out, float* gwork, int lo, int* ones, int nones, void* stream);
+int bsc_momentum_steps(int loss, const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,
+                       const double* W, int D_IN, int D_OUT, int B, int P, unsigned long long seed, int iteration,
+                       float max_norm, double qscale, int E, float lr, float momentum, float decay, float prox,
+                       float* delta, long long* qdelta, float* loss_out, float* vwork, int lo, int* ones, int nones,
+                       void* stream);
 int bsc_topk_rows(float* delta, long long* qdelta, int P, int D, int k, int* kept, void* stream);
 int bsc_gram_stacked_range(const float* X, int U1, const float* X2, int U2, long long stride2, int D, int kchunk,
                            int p0, int p1, double* part, double* gram, unsigned int* count, const double* nn,

@@ -490,6 +490,218 @@ BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_local_steps(
 }  // namespace
 
 // =====================================================================================
+// K1m: K1e's E local steps under the reference clients' optimiser (--local-momentum M, --local-decay LAMBDA,
+// --local-prox MU; docs/QUIRKS.md Q20): heavy-ball momentum m, weight decay lambda and a FedProx proximal weight mu.
+//   a_0 = 0, v_0 = 0;  step e: w_e = (float)W + a_e, minibatch e (K1e's tags), g_e and c_e as K1e,
+//   h_e = c_e g_e + lambda w_e + mu a_e (only the data gradient is clipped; the bias entries decay too),
+//   v_{e+1} = m v_e + h_e (PyTorch's SGD: dampening 0, no Nesterov), a_{e+1} = a_e - lr v_{e+1};
+//   delta = a_E (not clipped again), qdelta = quantize(delta), loss = the last step's mean row loss.
+// K1e's workgroup, draws, 256-feature tile with its 20-float skew, logits + Gram pass and fp64 clip coefficient; what
+// is its own:
+//   v       MOM only: the velocity is a second resident vector beside a.  A_IN_LDS: in dynamic LDS behind a
+//           (v = ls_a + nparam); else in the peer's row of the caller's fp32 [P, nparam] workspace vwork, which like
+//           its delta row no other workgroup touches and which stays L2-hot.  v_0 = 0 is never stored: step 0 takes
+//           its v as zero (a uniform branch), so the workspace needs no clearing and launches may share it
+//   MOM=0   m = 0: there is no v at all, h_e goes straight into a; LDS and cost are K1e's, no workspace
+//   update  fused into the dW MFMA pass: the lane that owns a[c][k] reads v[c][k], forms h from its accumulator, its
+//           own a (and, when lambda != 0 -- a uniform branch -- (float)W[c][k] from L2 again), writes v and a.  Every
+//           entry of a and v has one owner and every entry is met once per step (the tiles cover [D_OUT][D_IN]), so
+//           the decay and proximal terms need no pass of their own, no raw-gradient scratch and no barrier; the
+//           tid < D_OUT threads treat the bias entries the same way
+// LDS: K1e's 31016 B static.  MOM = false: plus at most 32 KiB of a = 62.3 KiB, inside the default 64 KiB.  MOM = true
+// and A_IN_LDS: plus at most 64 KiB of a and v = 94.3 KiB, raised once per instance with hipFuncSetAttribute (one
+// workgroup per CU serves the 100 peers of a round: occupancy is not what bounds it).
+// No atomics, no reduction whose order depends on timing: two runs give the same bytes.
+// =====================================================================================
+namespace {
+template <class Loss, bool A_IN_LDS, bool MOM>
+BSC_NO_PK_F32 __global__ void __launch_bounds__(SM_THREADS) k_momentum_steps(
+    const float* X, const int* y, const long long* off, const int* ntrain, const int* pid, const double* W, int D_IN,
+    int D_OUT, int B, int P, unsigned long long seed, int iteration, float max_norm, double qscale, int E, float lr,
+    float mom, float decay, float prox, float* delta, long long* qdelta, float* loss, float* vwork, int lo, int* ones,
+    int nones) {
+  BSC_SET_PRIO(BSC_PRIO_CRITICAL);
+  if (ones != nullptr && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < nones; i += blockDim.x) ones[i] = 1;
+  extern __shared__ float ls_a[];         // A_IN_LDS: a [nparam], then v [nparam] when MOM; else unused (0 bytes)
+  __shared__ float xs[16 * LS_KS];        // one K tile of the minibatch rows, transformed; rows >= Bq are zero
+  __shared__ float red[4][16][16];        // per-wave partial logits [s][c]
+  __shared__ float gram[4][16][16];       // per-wave partial Gram [s][t] of the transformed rows
+  __shared__ float G[16][16];             // d(mean loss) / d(logits)
+  __shared__ int bidx[LS_MAX_E][16];      // every step's minibatch
+  __shared__ double nrm[SM_THREADS / 64];
+  __shared__ float scale_sh;
+  const int p = blockIdx.x;
+  if (p >= P) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  const int li = lo >= 0 ? pid[p] - lo : p;
+  const long long offp = off[li];
+  const int n = ntrain[li];
+  const int Bq = min(B, n);
+  float* dst = delta + (size_t)p * nparam;
+  float* a = A_IN_LDS ? ls_a : dst;
+  float* v = !MOM ? nullptr : A_IN_LDS ? ls_a + nparam : vwork + (size_t)p * nparam;
+  const bool wd = decay != 0.f;
+  // 1. the E minibatches, one lane per step, as K1e; a_0 = 0
+  if (tid < E) {
+    int cnt = 0;
+    uint32_t ctr = 0;
+    const uint32_t tag = 0x5EEDu ^ ((uint32_t)tid << 16);
+    while (cnt < Bq) {
+      u4 r = philox(u4{(uint32_t)pid[p], (uint32_t)iteration, ctr++, tag}, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (cnt >= Bq) break;
+        const int c = (int)((q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w) % (uint32_t)n);
+        bool dup = false;
+        for (int t = 0; t < cnt; ++t) dup |= bidx[tid][t] == c;
+        if (!dup) bidx[tid][cnt++] = c;
+      }
+    }
+    for (int t = cnt; t < 16; ++t) bidx[tid][t] = -1;
+  }
+  for (int i = tid; i < nparam; i += SM_THREADS) a[i] = 0.f;
+  __syncthreads();
+  const int ktiles = (D_IN + LS_KT - 1) / LS_KT;
+  const int row = lane & 15, kk = lane >> 4;   // MFMA operand coordinates of this lane
+  for (int e = 0; e < E; ++e) {
+    const int* bi = bidx[e];
+    auto stage = [&](int kt) __attribute__((always_inline)) {  // (x - 0.5) / 0.5; zero padding
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      for (int i = tid; i < 16 * kw; i += SM_THREADS) {
+        const int s = i / kw, k = i % kw;
+        float xv = 0.f;
+        if (s < Bq) xv = (X[(offp + bi[s]) * (long long)D_IN + k0 + k] - 0.5f) * 2.0f;
+        xs[s * LS_KS + k] = xv;
+      }
+    };
+    // the owner's update of entry i from its clipped data gradient cg = c_e g_e[i]: h, then v (MOM) and a
+    auto update = [&](int i, float cg) __attribute__((always_inline)) {
+      const float ai = a[i];
+      float h = cg + prox * ai;
+      if (wd) h += decay * ((float)W[i] + ai);
+      if (MOM) {
+        if (e > 0) h += mom * v[i];
+        v[i] = h;
+      }
+      a[i] = ai - lr * h;
+    };
+    // 2. logits of w_e = (float)W + a and the rows' Gram, in one pass over the K tiles (the 4 waves split a tile)
+    {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f}, gacc = {0.f, 0.f, 0.f, 0.f};
+      for (int kt = 0; kt < ktiles; ++kt) {
+        const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+        __syncthreads();  // the tile's last readers (the previous tile, or the previous step's dW pass) are done
+        stage(kt);
+        __syncthreads();
+        const int ksteps = (kw + 3) / 4;
+        const int per = (ksteps + 3) / 4;
+        for (int st = wid * per; st < min(ksteps, (wid + 1) * per); ++st) {
+          const int k = st * 4 + kk;
+          const bool in = k < kw;
+          const float av = in ? xs[row * LS_KS + k] : 0.f;
+          float bv = 0.f;
+          if (in && row < D_OUT) bv = (float)W[row * D_IN + k0 + k] + a[row * D_IN + k0 + k];
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+          gacc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, av, gacc, 0, 0, 0);   // A[s][k] and B[k][t]: one register
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        red[wid][kk * 4 + r][row] = acc[r];
+        gram[wid][kk * 4 + r][row] = gacc[r];
+      }
+    }
+    __syncthreads();
+    // 3. the loss and G on rows s < Bq (one thread per row), as K1
+    if (tid < 16) {
+      const int s = tid;
+      if (s < Bq) {
+        float* lg = red[0][s];   // the row's logits, summed in place (LDS: the label indexes them)
+        for (int c = 0; c < D_OUT; ++c)
+          lg[c] = red[0][s][c] + red[1][s][c] + red[2][s][c] + red[3][s][c] +
+                  ((float)W[D_OUT * D_IN + c] + a[D_OUT * D_IN + c]);
+        const float l = Loss::row(lg, D_OUT, y[offp + bi[s]], Bq, G[s]);
+        for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
+        red[1][s][0] = l;
+      } else {
+        for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
+      }
+    }
+    __syncthreads();
+    if (tid == 0 && e == E - 1) {
+      float l = 0.f;
+      for (int s = 0; s < Bq; ++s) l += red[1][s][0];
+      loss[p] = l / (float)max(Bq, 1);
+    }
+    // 4. the clip coefficient from G and the Gram: thread (s, t) holds (G_s.G_t)(x_s.x_t + 1)
+    {
+      const int s = tid >> 4, t = tid & 15;
+      double gg = 0.0;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) gg += (double)G[s][c] * (double)G[t][c];
+      const float xx = gram[0][s][t] + gram[1][s][t] + gram[2][s][t] + gram[3][s][t];
+      double sq = gg * ((double)xx + 1.0);
+      for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+      if (lane == 0) nrm[wid] = sq;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const float tot = (float)sqrt(fmax(nrm[0] + nrm[1] + nrm[2] + nrm[3], 0.0));
+      const float coef = max_norm / (tot + 1e-6f);
+      scale_sh = coef < 1.f ? coef : 1.f;
+    }
+    __syncthreads();
+    const float sc = scale_sh;
+    // 5. dW[c][k] = sum_s G[s][c] xs[s][k] via f32 MFMA, each entry's owner applying the update from its accumulator;
+    // the last tile is still resident: it goes first
+    for (int q = 0; q < ktiles; ++q) {
+      const int kt = (ktiles - 1 + q) % ktiles;
+      const int k0 = kt * LS_KT, kw = min(LS_KT, D_IN - k0);
+      if (q > 0) {
+        __syncthreads();
+        stage(kt);
+        __syncthreads();
+      }
+      const int ntiles = (kw + 15) / 16;
+      for (int t = wid; t < ntiles; t += 4) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const int k = t * 16 + row;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const int s = ks * 4 + kk;
+          const float av = G[s][row];  // A[c = row][s]
+          const float bv = (k < kw) ? xs[s * LS_KS + k] : 0.f;
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = kk * 4 + r;
+          if (c < D_OUT && k < kw) update(c * D_IN + k0 + k, sc * acc[r]);
+        }
+      }
+    }
+    if (tid < D_OUT) {
+      float db = 0.f;
+      for (int s = 0; s < 16; ++s) db += G[s][tid];
+      update(D_OUT * D_IN + tid, sc * db);
+    }
+    // (the next step's first barrier, or the one below, orders these writes of a before their readers; v has no
+    // reader but its owner)
+  }
+  __syncthreads();
+  // 6. delta = a_E, quantised like updateFloatToInt
+  long long* qd = qdelta + (size_t)p * nparam;
+  for (int i = tid; i < nparam; i += SM_THREADS) {
+    const float r = a[i];
+    if (A_IN_LDS) dst[i] = r;
+    qd[i] = quantize(r, qscale);
+  }
+}
+}  // namespace
+
+// =====================================================================================
 // K1p: E DP-SGD steps of the same linear scorer per round (--dp-clip C [--dp-sigma S]; docs/QUIRKS.md Q18): each
 // example's gradient is clipped to C before the minibatch rows are summed, N(0, (S C)^2) is added to the sum, and
 // the sum is divided by the batch size.
@@ -2433,6 +2645,59 @@ extern "C" int bsc_local_steps(int loss, const float* X, const int* y, const lon
                    : local_steps_launch<CrossEntropyLoss>((hipStream_t)stream, nparam, X, y, off, ntrain, pid, W, D_IN,
                                                           D_OUT, B, P, seed, iteration, max_norm, qscale, E, lr, delta,
                                                           qdelta, loss_out, lo, ones, nones);
+}
+
+namespace {
+template <class Loss, bool MOM>
+int momentum_steps_launch(hipStream_t s, int nparam, const float* X, const int* y, const long long* off,
+                          const int* ntrain, const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
+                          unsigned long long seed, int iteration, float max_norm, double qscale, int E, float lr,
+                          float mom, float decay, float prox, float* delta, long long* qdelta, float* loss,
+                          float* vwork, int lo, int* ones, int nones) {
+  if (nparam <= LS_LDS_A) {
+    if (MOM) {
+      // a and v beside the static 31016 B pass the default 64 KiB (K1m's header): opt in once per instance
+      static const hipError_t optin =
+          hipFuncSetAttribute((const void*)k_momentum_steps<Loss, true, MOM>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * LS_LDS_A * (int)sizeof(float));
+      if (optin != hipSuccess) return (int)optin;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_momentum_steps<Loss, true, MOM>), dim3(P), dim3(SM_THREADS),
+                       (size_t)(MOM ? 2 : 1) * nparam * sizeof(float), s, X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P,
+                       seed, iteration, max_norm, qscale, E, lr, mom, decay, prox, delta, qdelta, loss, vwork, lo, ones,
+                       nones);
+  } else {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_momentum_steps<Loss, false, MOM>), dim3(P), dim3(SM_THREADS), 0, s, X, y, off,
+                       ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, E, lr, mom, decay, prox,
+                       delta, qdelta, loss, vwork, lo, ones, nones);
+  }
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+// K1m: K1e's E local steps with momentum mom in [0, 1), weight decay >= 0 and proximal weight prox >= 0 (all finite).
+// vwork: fp32 [P, nparam] velocity workspace, needed when mom > 0 and nparam > LS_LDS_A (else nullable, untouched); it
+// needs no clearing.  The other arguments and limits are K1e's.
+extern "C" int bsc_momentum_steps(int loss, const float* X, const int* y, const long long* off, const int* ntrain,
+                                  const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
+                                  unsigned long long seed, int iteration, float max_norm, double qscale, int E, float lr,
+                                  float momentum, float decay, float prox, float* delta, long long* qdelta,
+                                  float* loss_out, float* vwork, int lo, int* ones, int nones, void* stream) {
+  if (D_IN <= 0 || D_OUT > 16 || B > 16 || E < 1 || E > LS_MAX_E || !(lr > 0.f) || loss < 0 || loss > 1) return -1;
+  if (!(momentum >= 0.f && momentum < 1.f) || !(decay >= 0.f && decay < INFINITY) || !(prox >= 0.f && prox < INFINITY))
+    return -1;
+  const int nparam = D_OUT * D_IN + D_OUT;
+  const bool m = momentum > 0.f;
+  if (m && nparam > LS_LDS_A && vwork == nullptr) return -1;
+  if (P <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+#define BSC_MOM_LAUNCH(LOSS, MOMV)                                                                                    \
+  momentum_steps_launch<LOSS, MOMV>(s, nparam, X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration,         \
+                                    max_norm, qscale, E, lr, momentum, decay, prox, delta, qdelta, loss_out, vwork,   \
+                                    lo, ones, nones)
+  if (loss == 1) return m ? BSC_MOM_LAUNCH(MarginLoss, true) : BSC_MOM_LAUNCH(MarginLoss, false);
+  return m ? BSC_MOM_LAUNCH(CrossEntropyLoss, true) : BSC_MOM_LAUNCH(CrossEntropyLoss, false);
+#undef BSC_MOM_LAUNCH
 }
 
 namespace {

@@ -59,6 +59,9 @@ struct TaskCfg {  // the softmax task's resident data and the pre-step's constan
   float dp_sigma = 0.f;  // its noise multiplier S
   int lot = 0;           // examples per local step (--lot-size); above 0 the pre-step queues k_lot_steps for every step
   float* lot_g = nullptr;   // its [P, nparam] step-gradient workspace (caller-owned; see bsc_lot_steps)
+  float mom = 0.f, decay = 0.f, prox = 0.f;   // the local optimiser (--local-momentum / -decay / -prox); any of them
+                                              // above 0: the pre-step queues k_momentum_steps (local_E steps, may be 1)
+  float* mom_v = nullptr;   // its [P, nparam] velocity workspace (caller-owned; see bsc_momentum_steps)
   hipStream_t gram;
   const float* X;
   const int *y, *ntrain, *pid, *rows_arange;
@@ -514,6 +517,8 @@ extern "C" int bsc_round_bind_task(void* ctx, void* gram_stream, const float* X,
   t.dp_sigma = 0.f;
   t.lot = 0;
   t.lot_g = nullptr;
+  t.mom = t.decay = t.prox = 0.f;
+  t.mom_v = nullptr;
   t.bound = 1;
   return 0;
 }
@@ -566,6 +571,22 @@ extern "C" int bsc_round_task_lot(void* ctx, int L, float* gwork) {
   if (c == nullptr || !c->task.bound || L < 0 || L > 256) return -1;
   c->task.lot = L;
   c->task.lot_g = gwork;
+  return 0;
+}
+
+// The bound task's local optimiser (all 0, the default of every bind: off; any above 0: the pre-step queues
+// k_momentum_steps in place of k_local_steps / the single step -- local_E steps, which may be 1, at rate local_lr with
+// momentum m in [0, 1), weight decay and proximal weight >= 0).  vwork: the caller's fp32 [P, nparam] workspace for
+// bsc_momentum_steps (nullable where that is).  The lot and DP-SGD branches go first: the task does not combine them.
+extern "C" int bsc_round_task_momentum(void* ctx, float m, float decay, float prox, float* vwork) {
+  RoundCtx* c = (RoundCtx*)ctx;
+  if (c == nullptr || !c->task.bound || !(m >= 0.f && m < 1.f) || !(decay >= 0.f && decay < INFINITY) ||
+      !(prox >= 0.f && prox < INFINITY))
+    return -1;
+  c->task.mom = m;
+  c->task.decay = decay;
+  c->task.prox = prox;
+  c->task.mom_v = vwork;
   return 0;
 }
 
@@ -657,6 +678,10 @@ extern "C" int bsc_round_prestep_slot(void* ctx, const double* W, int it, int do
     RC_CHECK(bsc_dpsgd_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it, t.qs,
                              t.dp_clip, t.dp_sigma, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss, t.lo, ones,
                              c->spec_cap, gs));
+  else if (t.mom > 0.f || t.decay > 0.f || t.prox > 0.f)
+    RC_CHECK(bsc_momentum_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it,
+                                t.max_norm, t.qs, t.local_E, t.local_lr, t.mom, t.decay, t.prox, p.delta, p.qdelta,
+                                p.loss, t.mom_v, t.lo, ones, c->spec_cap, gs));
   else if (t.local_E > 1)
     RC_CHECK(bsc_local_steps(t.loss, t.X, t.y, t.off, t.ntrain, t.pid, W, t.d_in, t.d_out, t.B, t.P, t.seed, it,
                              t.max_norm, t.qs, t.local_E, t.local_lr, p.delta, p.qdelta, p.loss, t.lo, ones,

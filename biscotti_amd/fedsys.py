@@ -39,6 +39,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lot-size", type=int, default=0, metavar="L",
                     help="examples each local step draws, up to 256, in place of the batch size (k_lot_steps; mnist and "
                          "lfw, 0 = off)")
+    ap.add_argument("--local-momentum", type=float, default=0.0, metavar="M",
+                    help="heavy-ball momentum of the local steps, 0 <= M < 1 (k_momentum_steps; mnist and lfw, not with "
+                         "--dp-clip or --lot-size; 0 = off)")
+    ap.add_argument("--local-decay", type=float, default=0.0, metavar="LAMBDA",
+                    help="weight decay of the local steps, >= 0")
+    ap.add_argument("--local-prox", type=float, default=0.0, metavar="MU",
+                    help="FedProx proximal weight of the local steps, >= 0")
     return ap
 
 
@@ -63,7 +70,8 @@ def main(argv=None) -> int:
 
     comm = Comm.init(device=cfg.device)
     eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
-                       dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size)
+                       dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size, local_momentum=ns.local_momentum,
+                       local_decay=ns.local_decay, local_prox=ns.local_prox)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

@@ -26,7 +26,8 @@ class SoftmaxTask:
     def __init__(self, peers: range, num_peers: int, device, seed: int, poisoned: set[int] | None = None,
                  batch_size: int = 10, data_dir: str | None = None, federation: D.MnistFederation | None = None,
                  dims: tuple | None = None, loss: str = "ce", topk: float = 1.0, local_steps: int = 1,
-                 local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0, lot_size: int = 0):
+                 local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0, lot_size: int = 0,
+                 local_momentum: float = 0.0, local_decay: float = 0.0, local_prox: float = 0.0):
         if loss not in ("ce", "margin"):
             raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
         if not 0.0 < topk <= 1.0:
@@ -55,6 +56,16 @@ class SoftmaxTask:
         # above that is on -- DP-SGD's, else the local steps' -- through K.lot_steps (any local_steps / local_lr).
         # batch_size keeps sizing the noisers' scale and RONI's rows.  0: off, today's branches
         self.lot_size = int(lot_size)
+        # the local optimiser (docs/QUIRKS.md Q20): heavy-ball momentum, weight decay and a FedProx proximal weight on
+        # the local steps (K.momentum_steps, for any local_steps / local_lr; the velocity starts at 0 every round, so
+        # the step is still a function of (W, peer, iteration)).  All 0: off, today's branches
+        self.local_momentum, self.local_decay, self.local_prox = K.check_local_optimiser(local_momentum, local_decay,
+                                                                                         local_prox)
+        self.local_opt = self.local_momentum > 0 or self.local_decay > 0 or self.local_prox > 0
+        if self.local_opt and (self.dp_clip > 0 or self.lot_size > 0):
+            raise ValueError("local_momentum / local_decay / local_prox do not combine with dp_clip or lot_size: "
+                             "DP-SGD's sensitivity argument (Q18) covers plain steps only, and the lot kernel has no "
+                             "velocity; neither is extended here")
         # "margin": the same linear scorer trained as SVMModel (svm_model.py under nn.MultiLabelMarginLoss with
         # the single target, client.py:28); evaluation, train_error and roni_rows are argmax-based: the same
         self.loss = loss
@@ -128,6 +139,11 @@ class SoftmaxTask:
             delta, qdelta, loss = K.dpsgd_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
                                                 self.batch, self.seed, iteration, self.dp_clip, self.dp_sigma,
                                                 self.local_steps, self.local_lr, loss=self.loss, lo=self.peers[0])
+        elif self.local_opt:
+            delta, qdelta, loss = K.momentum_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
+                                                   self.batch, self.seed, iteration, self.local_steps, self.local_lr,
+                                                   self.local_momentum, self.local_decay, self.local_prox,
+                                                   loss=self.loss, lo=self.peers[0])
         elif self.local_steps > 1:
             delta, qdelta, loss = K.local_steps(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
                                                 self.batch, self.seed, iteration, self.local_steps, self.local_lr,
@@ -310,13 +326,15 @@ MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax",
               topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0,
-              dp_sigma: float = 0.0, lot_size: int = 0, **kw):
+              dp_sigma: float = 0.0, lot_size: int = 0, local_momentum: float = 0.0, local_decay: float = 0.0,
+              local_prox: float = 0.0, **kw):
     """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
     loss="margin"); creditcard has its logistic model only.  topk < 1: mnist / lfw's peers send top-k sparsified
     updates (SoftmaxTask's topk).  local_steps > 1: they run that many local SGD steps per round at rate local_lr
     (SoftmaxTask's local_steps).  dp_clip > 0: their steps are DP-SGD steps, per-example clip dp_clip and noise
     multiplier dp_sigma (SoftmaxTask's dp_clip).  lot_size > 0: every step draws lot_size examples, up to 256, in
-    place of batch_size (SoftmaxTask's lot_size)."""
+    place of batch_size (SoftmaxTask's lot_size).  local_momentum / local_decay / local_prox > 0: the local steps run
+    under heavy-ball momentum, weight decay and a FedProx proximal weight (SoftmaxTask's local_momentum)."""
     if model not in MODELS:
         raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
     if model == "svm" and dataset == "creditcard":
@@ -329,12 +347,16 @@ def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, mod
         raise ValueError("dp_clip / dp_sigma need mnist or lfw: creditcard's logistic step already noises at the source")
     if lot_size != 0 and dataset == "creditcard":
         raise ValueError("lot_size needs mnist or lfw: creditcard's logistic step draws batch_size examples")
+    if (local_momentum != 0 or local_decay != 0 or local_prox != 0) and dataset == "creditcard":
+        raise ValueError("local_momentum / local_decay / local_prox need mnist or lfw: creditcard's logistic step is a "
+                         "single noisy step")
     loss = "margin" if model == "svm" else "ce"
     kw["topk"] = topk
     if dataset != "creditcard":
         kw["local_steps"], kw["local_lr"] = local_steps, local_lr
         kw["dp_clip"], kw["dp_sigma"] = dp_clip, dp_sigma
         kw["lot_size"] = lot_size
+        kw["local_momentum"], kw["local_decay"], kw["local_prox"] = local_momentum, local_decay, local_prox
     if dataset == "mnist":
         kw.pop("epsilon", None)
         kw.pop("colluders", None)

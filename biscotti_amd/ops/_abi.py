@@ -59,6 +59,7 @@ SIGNATURES = {
     "bsc_local_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, I, F, P, P, P, I, P, I, P],
     "bsc_dpsgd_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, D, F, F, I, F, P, P, P, I, P, I, P],
     "bsc_lot_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, F, F, I, F, P, P, P, P, I, P, I, P],
+    "bsc_momentum_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, I, F, F, F, F, P, P, P, P, I, P, I, P],
     "bsc_topk_rows": [P, P, I, I, I, P, P],
     "bsc_logreg_step": [P, P, P, P, P, P, I, I, I, U64, P, D, D, P, D, P, P, P],
     "bsc_dp_noise": [P, I, I, P, I, P, U64, I, P, P],
@@ -97,6 +98,7 @@ SIGNATURES = {
     "bsc_round_task_local": [P, I, F],
     "bsc_round_task_dpsgd": [P, F, F],
     "bsc_round_task_lot": [P, I, P],
+    "bsc_round_task_momentum": [P, F, F, F, P],
     "bsc_round_add_pre_slot": [P, P, P, P, P, P, P, P, P, P, P, P, P],
     "bsc_round_prestep_slot": [P, P, I, I],
     "bsc_round_set_nn_table": [P, P],

@@ -605,14 +605,20 @@ class NativeSecAgg:
             _check(hip().bsc_round_task_topk(self.ctx, task.topk_k), "round_task_topk")
         dp = getattr(task, "dp_clip", 0.0) > 0
         lot = getattr(task, "lot_size", 0)
-        if getattr(task, "local_steps", 1) > 1 or dp or lot:   # k_local_steps (a bind resets it to one step); DP-SGD's
-            _check(hip().bsc_round_task_local(self.ctx, task.local_steps, task.local_lr), "round_task_local")   # and the lot's E, lr
+        opt = getattr(task, "local_opt", False)
+        if getattr(task, "local_steps", 1) > 1 or dp or lot or opt:   # k_local_steps (a bind resets it to one step); DP-SGD's
+            _check(hip().bsc_round_task_local(self.ctx, task.local_steps, task.local_lr), "round_task_local")   # the lot's and the optimiser's E, lr
         if dp:   # the pre-step queues k_dpsgd_steps in place of the other steps (a bind resets it to off)
             _check(hip().bsc_round_task_dpsgd(self.ctx, task.dp_clip, task.dp_sigma), "round_task_dpsgd")
         if lot:  # the pre-step queues k_lot_steps in place of the other three (a bind resets it to off)
             from . import ml as K
             self.lot_g = K.lot_workspace(P, d, getattr(task, "dp_clip", 0.0), dev)   # the steps of one stream share it
             _check(hip().bsc_round_task_lot(self.ctx, lot, _ptr(self.lot_g)), "round_task_lot")
+        if opt:  # the pre-step queues k_momentum_steps in place of k_local_steps / the step (a bind resets it to off)
+            from . import ml as K
+            self.mom_v = K.momentum_workspace(P, d, task.local_momentum, dev)   # the steps of one stream share it
+            _check(hip().bsc_round_task_momentum(self.ctx, task.local_momentum, task.local_decay, task.local_prox,
+                                                 _ptr(self.mom_v)), "round_task_momentum")
 
         def ev():
             e = torch.cuda.Event()

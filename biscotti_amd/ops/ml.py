@@ -7,6 +7,8 @@ float rounding and GPU numerics tests compare against it.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -310,6 +312,82 @@ def lot_workspace(P: int, nparam: int, clip: float, device):
     """bsc_lot_steps' step-gradient workspace: fp32 [P, nparam] where the update does not live in LDS (LS_LDS_A = 8192
     parameters) and the rule is the mean's clip; None where the kernel needs none."""
     if clip > 0 or nparam <= 8192:
+        return None
+    return torch.empty((P, nparam), dtype=torch.float32, device=device)
+
+
+def check_local_optimiser(momentum, decay, prox):
+    """The local optimiser's three weights as floats, or ValueError: momentum in [0, 1), decay and prox finite >= 0."""
+    ok = 0 <= momentum < 1 and 0 <= decay < math.inf and 0 <= prox < math.inf   # a NaN fails every comparison
+    if not ok:
+        raise ValueError(f"the local optimiser takes a momentum in [0, 1), a weight decay >= 0 and a proximal weight "
+                         f">= 0, not local_momentum={momentum!r} local_decay={decay!r} local_prox={prox!r}")
+    return float(momentum), float(decay), float(prox)
+
+
+def momentum_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, E, lr, momentum=0.0, decay=0.0, prox=0.0,
+                   loss="ce", max_norm=100.0, qscale=1e4, lo=-1):
+    """local_steps under the reference clients' optimiser (k_momentum_steps, docs/QUIRKS.md Q20): with a_0 = v_0 = 0,
+    step e takes local_steps' minibatch, scorer w_e = float32(W) + a_e and clipped gradient c_e g_e, and
+    h_e = c_e g_e + decay * w_e + prox * a_e, v_{e+1} = momentum * v_e + h_e, a_{e+1} = a_e - lr * v_{e+1}
+    (torch.optim.SGD with dampening 0 and no Nesterov; prox * a_e is FedProx's mu (w - W)).  Returns (delta = a_E fp32
+    [P, nparam], not clipped again, qdelta int64, loss fp32 [P] of the last step); the other arguments are
+    softmax_step's.  All three at 0 is local_steps' mathematics."""
+    if loss not in ("ce", "margin"):
+        raise ValueError(f"unsupported loss {loss!r} (ce or margin)")
+    if E != int(E) or not 1 <= E <= LOCAL_STEPS_MAX or not lr > 0:
+        raise ValueError(f"momentum steps: an integer E in 1..{LOCAL_STEPS_MAX} and a rate lr > 0, not E={E!r} lr={lr!r}")
+    momentum, decay, prox = check_local_optimiser(momentum, decay, prox)
+    E, lr = int(E), float(lr)
+    P = pid.numel()
+    nw = d_out * d_in
+    nparam = nw + d_out
+    dev = X.device
+    delta = torch.empty((P, nparam), dtype=torch.float32, device=dev)
+    qdelta = torch.empty((P, nparam), dtype=torch.int64, device=dev)
+    lossv = torch.empty((P,), dtype=torch.float32, device=dev)
+    if dev.type == "cuda":
+        assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+        assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
+        assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
+        vwork = momentum_workspace(P, nparam, momentum, dev)
+        _check(hip().bsc_momentum_steps(int(loss == "margin"), _p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in,
+                                        d_out, B, P, seed & (2**64 - 1), iteration, float(max_norm), float(qscale), E,
+                                        lr, momentum, decay, prox, _p(delta), _p(qdelta), _p(lossv), _p(vwork), int(lo),
+                                        None, 0, _stream()), "momentum_steps")
+        return delta, qdelta, lossv
+    loss_rows = _margin_rows if loss == "margin" else _ce_rows
+    Wm = W.to(torch.float32)
+    pids = pid.tolist()
+    if lo >= 0:
+        offs = [int(off[q - lo]) for q in pids]
+        ns = [int(ntrain[q - lo]) for q in pids]
+    else:
+        offs, ns = off.tolist(), ntrain.tolist()
+    for p in range(P):
+        a, v = torch.zeros(nparam), torch.zeros(nparam)
+        for e in range(E):
+            idx = minibatch_indices(pids[p], iteration, ns[p], B, seed, tag=0x5EED ^ (e << 16))
+            rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
+            xb = (X[rows] - 0.5) / 0.5
+            w = Wm + a
+            logits = xb @ w[:nw].view(d_out, d_in).T + w[nw:]
+            last, g = loss_rows(logits, y[rows].long())
+            flat = torch.cat([(g.T @ xb).reshape(-1), g.sum(0)])
+            coef = max_norm / (float(torch.linalg.vector_norm(flat)) + 1e-6)
+            v = momentum * v + (flat * min(coef, 1.0) + decay * w + prox * a)
+            a = a - lr * v
+        delta[p] = a
+        qdelta[p] = torch.from_numpy((a.double().numpy() * qscale).astype(np.int64))
+        lossv[p] = last
+    return delta, qdelta, lossv
+
+
+def momentum_workspace(P: int, nparam: int, momentum: float, device):
+    """bsc_momentum_steps' velocity workspace: fp32 [P, nparam] where there is a velocity (momentum > 0) and it does
+    not live in LDS beside the update (LS_LDS_A = 8192 parameters); None where the kernel needs none.  The kernel never
+    reads what an earlier launch left there."""
+    if not momentum > 0 or nparam <= 8192:
         return None
     return torch.empty((P, nparam), dtype=torch.float32, device=device)
 

@@ -77,6 +77,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="examples each local step draws, up to 256, in place of the batch size (k_lot_steps; mnist and "
                          "lfw, 0 = off, today's steps; the batch size keeps sizing the noisers' scale and RONI).  A "
                          "chain does not record it: --resume needs the same --lot-size")
+    ap.add_argument("--local-momentum", type=float, default=0.0, metavar="M",
+                    help="heavy-ball momentum of the local steps, 0 <= M < 1 (k_momentum_steps, for any --local-steps; "
+                         "mnist and lfw, not with --dp-clip or --lot-size; 0 = off).  A chain records none of the three: "
+                         "--resume needs the same --local-momentum, --local-decay and --local-prox")
+    ap.add_argument("--local-decay", type=float, default=0.0, metavar="LAMBDA",
+                    help="weight decay of the local steps, >= 0: LAMBDA times the local model joins each step's gradient")
+    ap.add_argument("--local-prox", type=float, default=0.0, metavar="MU",
+                    help="FedProx proximal weight of the local steps, >= 0: MU times (local model - global model) joins "
+                         "each step's gradient")
     return ap
 
 
@@ -106,7 +115,8 @@ def main(argv=None) -> int:
 
     comm = Comm.init(device=cfg.device, timeout_s=cfg.comm_timeout_s)
     eng = BiscottiEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
-                         dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size)
+                         dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size, local_momentum=ns.local_momentum,
+                         local_decay=ns.local_decay, local_prox=ns.local_prox)
     eng.sign_device = ns.device_sign
     srv, flood = None, [a for a in ns.rpc_flood.split(",") if a.strip()] if comm.rank == 0 else []
     if ns.rpc_listen and comm.rank == 0:
@@ -179,7 +189,8 @@ def _rpc_peer_main(cfg, ns) -> int:
     cfg = dataclasses.replace(cfg, device="cpu")
     peer = RpcPeer(cfg, cfg.node_index, addrs, timeout_s=cfg.comm_timeout_s if cfg.comm_timeout_s < 300 else 30.0,
                    model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
-                   dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size)
+                   dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size, local_momentum=ns.local_momentum,
+                   local_decay=ns.local_decay, local_prox=ns.local_prox)
     try:
         import time
 

@@ -80,7 +80,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
                      FaultsMixin):
     def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0,
                  local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0,
-                 lot_size: int = 0):
+                 lot_size: int = 0,
+                 local_momentum: float = 0.0, local_decay: float = 0.0, local_prox: float = 0.0):
         cfg.validate()
         self.cfg = cfg
         # the ledger's model ("softmax", or "svm": the same scorer under the margin loss; models.make_task).  An
@@ -99,6 +100,9 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         # lots (models.make_task): examples per local step, up to 256; 0: off, batch_size of them.  An engine argument
         # like local_steps, and like it not recorded by a chain
         self.lot_size = lot_size
+        # the local optimiser (models.make_task): momentum, weight decay and proximal weight of the local steps; 0: off.
+        # Engine arguments like local_steps, and like it not recorded by a chain
+        self.local_momentum, self.local_decay, self.local_prox = local_momentum, local_decay, local_prox
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -140,7 +144,8 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
         self.colluders = colluders
         self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk,
                               local_steps=local_steps, local_lr=local_lr, dp_clip=dp_clip, dp_sigma=dp_sigma,
-                              lot_size=lot_size, poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
+                              lot_size=lot_size, local_momentum=local_momentum, local_decay=local_decay,
+                              local_prox=local_prox, poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
                               epsilon=cfg.epsilon, colluders=colluders)
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
         # ---- ledger / protocol state

@@ -47,7 +47,8 @@ class FedSysResult:
 class FedSysEngine:
     def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0,
                  local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0,
-                 lot_size: int = 0):
+                 lot_size: int = 0,
+                 local_momentum: float = 0.0, local_decay: float = 0.0, local_prox: float = 0.0):
         from ..data import dataset_dims
         from ..models import make_task
 
@@ -57,6 +58,8 @@ class FedSysEngine:
         self.local_steps, self.local_lr = local_steps, local_lr   # local SGD steps per round and their rate; 1: off
         self.dp_clip, self.dp_sigma = dp_clip, dp_sigma           # DP-SGD's per-example clip and noise multiplier; 0: off
         self.lot_size = lot_size                                  # examples per local step (up to 256); 0: batch_size
+        # the local steps' momentum, weight decay and proximal weight; 0: off
+        self.local_momentum, self.local_decay, self.local_prox = local_momentum, local_decay, local_prox
         self.comm = comm or Comm()
         self.R = rt()
         self.dev = self.comm.device if cfg.device != "cpu" else torch.device("cpu")
@@ -79,7 +82,8 @@ class FedSysEngine:
         poisoned = {p for p in self.local if probe.is_poisoner(p, True)}   # FedSys: >= (Q4)
         self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk,
                               local_steps=local_steps, local_lr=local_lr, dp_clip=dp_clip, dp_sigma=dp_sigma,
-                              lot_size=lot_size, poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
+                              lot_size=lot_size, local_momentum=local_momentum, local_decay=local_decay,
+                              local_prox=local_prox, poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
                               epsilon=cfg.epsilon, colluders=set())
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
         self.W = torch.zeros(self.d, dtype=torch.float64, device=self.dev)

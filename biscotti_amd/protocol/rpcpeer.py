@@ -40,7 +40,8 @@ class RpcPeer:
     def __init__(self, cfg: RunConfig, peer_id: int, addresses: list[str], host: str = "127.0.0.1",
                  port: int | None = None, timeout_s: float = 20.0, *, model: str = "softmax",
                  topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0,
-                 dp_sigma: float = 0.0, lot_size: int = 0):
+                 dp_sigma: float = 0.0, lot_size: int = 0, local_momentum: float = 0.0, local_decay: float = 0.0,
+                 local_prox: float = 0.0):
         from ..data import dataset_dims
         from ..models import make_task
         from .engine import _seed_bytes
@@ -56,7 +57,8 @@ class RpcPeer:
         self.model = model   # "softmax" or "svm" (models.make_task): every peer of a deployment takes the same one
         self.task = make_task(cfg.dataset, range(self.id, self.id + 1), self.N, torch.device("cpu"), cfg.seed,
                               model=model, topk=topk, local_steps=local_steps, local_lr=local_lr, dp_clip=dp_clip,
-                              dp_sigma=dp_sigma, lot_size=lot_size, poisoned=poisoned, batch_size=cfg.batch_size,
+                              dp_sigma=dp_sigma, lot_size=lot_size, local_momentum=local_momentum,
+                              local_decay=local_decay, local_prox=local_prox, poisoned=poisoned, batch_size=cfg.batch_size,
                               epsilon=cfg.epsilon)
         self.key = R.CommitKey.generate(self.d, 2)   # publicKey.go: s = 2 (every peer derives the same key)
         self.sk, self.pk = R.client_key_from_entropy(_seed_bytes(cfg.seed, "client", self.id))

@@ -3,7 +3,8 @@ functions and which torch / native calls hold the round's host thread.
 
     python scripts/prof_rounds.py [--warm 30] [--rounds 200] [--emulate-world N] [--device-sign] [--model svm]
                                   [--topk THETA] [--local-steps E] [--local-lr ETA] [--dp-clip C] [--dp-sigma S]
-                                  [--lot-size L] [--no-profile] [-o out.txt]
+                                  [--lot-size L] [--local-momentum M] [--local-decay LAMBDA] [--local-prox MU]
+                                  [--no-profile] [-o out.txt]
 
 --emulate-world N profiles rank 0 of an N-rank job (bench.py --emulate-world: the collectives filled locally).
 --device-sign sets engine.sign_device (the verifiers' signatures from k_schnorr_sign).  --model svm runs the rounds
@@ -11,6 +12,7 @@ with the margin-loss local step (k_margin_step) instead of k_softmax_step.  --to
 --local-steps E [--local-lr ETA] runs them with E local SGD steps per peer (k_local_steps instead of the step).
 --dp-clip C [--dp-sigma S] runs them with DP-SGD steps (k_dpsgd_steps instead of the step, for any --local-steps).
 --lot-size L runs them with lots of L examples per local step (k_lot_steps instead of the step).
+--local-momentum M / --local-decay LAMBDA / --local-prox MU run them under the local optimiser (k_momentum_steps).
 --no-profile times the same rounds without cProfile.  The last line printed is one JSON summary: ms per round
 (wall), the round thread's CPU us per round, the final drain's parts and the signer's stats.
 """
@@ -44,6 +46,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dp-clip", type=float, default=0.0)
     ap.add_argument("--dp-sigma", type=float, default=0.0)
     ap.add_argument("--lot-size", type=int, default=0)
+    ap.add_argument("--local-momentum", type=float, default=0.0)
+    ap.add_argument("--local-decay", type=float, default=0.0)
+    ap.add_argument("--local-prox", type=float, default=0.0)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("-o", "--out", default=None)
     return ap
@@ -55,7 +60,8 @@ def main():
     torch.set_num_threads(1)
     eng = BiscottiEngine(RunConfig(num_nodes=100, seed=0, max_iterations=10**9, host_threads=14, lazy_eval=True), comm,
                          model=a.model, topk=a.topk, local_steps=a.local_steps, local_lr=a.local_lr,
-                         dp_clip=a.dp_clip, dp_sigma=a.dp_sigma, lot_size=a.lot_size)
+                         dp_clip=a.dp_clip, dp_sigma=a.dp_sigma, lot_size=a.lot_size, local_momentum=a.local_momentum,
+                         local_decay=a.local_decay, local_prox=a.local_prox)
     eng.sign_device = a.device_sign
     for _ in range(a.warm):
         eng.run_round()
@@ -83,6 +89,7 @@ def main():
         print(txt[:6000])
     summary = {"model": eng.model, "topk": eng.topk, "local_steps": eng.local_steps, "local_lr": eng.local_lr,
                "dp_clip": eng.dp_clip, "dp_sigma": eng.dp_sigma, "lot_size": eng.lot_size,
+               "local_momentum": eng.local_momentum, "local_decay": eng.local_decay, "local_prox": eng.local_prox,
                "device_sign": a.device_sign, "profiled": pr is not None,
                "rounds": a.rounds, "ms_per_round": 1e3 * (t1 - t0) / a.rounds, "host_thread_us_per_round": 1e6 * (c1 - c0) / a.rounds,
                "drain_parts_ms": getattr(eng, "drain_parts_ms", None),

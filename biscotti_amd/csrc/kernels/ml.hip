@@ -4,6 +4,7 @@
 //       fixed-point quantisation -- one workgroup per virtual peer
 //       (ML/Pytorch/client.py:38-65, client_obj.py:73-77, DistSys/kyber.go:698-710); the same body under the
 //       multi-class margin loss is the SVM task's step (k_margin_step; svm_model.py, client.py:28)
+//   K1m the same step of a one-hidden-layer ReLU MLP (k_mlp_step; FedSys only), K2m its evaluation (k_mlp_eval)
 //   K1t top-k sparsification of the step's rows: per-row radix select on the fp32 magnitudes, in place
 //       (ML/code/linear_model.py:48-88)
 //   K3  batched logistic-regression step with DP noise at source (ML/code/logistic_model.py:92-140)
@@ -283,6 +284,287 @@ extern "C" __global__ void __launch_bounds__(SM_THREADS) k_margin_step(
     long long* qdelta, float* loss, int lo, int* ones, int nones) {
   linear_step_body<MarginLoss>(X, y, off, ntrain, pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, delta,
                                qdelta, loss, lo, ones, nones);
+}
+
+// =====================================================================================
+// K1m: local step of a one-hidden-layer MLP, x -> h = relu(W1 x + b1) -> logits = W2 h + b2, under cross-entropy.
+// H = 16 NCT hidden units (NCT = 1..4 column tiles of 16), D_OUT <= 16, B <= 16, any D_IN.  W fp64, flat in torch's
+// parameters() order: [W1 (H x D_IN, row-major) | b1 (H) | W2 (D_OUT x H, row-major) | b2 (D_OUT)].  The minibatch
+// draw, the transform, a shard shorter than B, the clip of the whole gradient, delta = -clipped gradient, the
+// quantisation and the per-peer loss are K1's.  One 256-thread workgroup per peer, the batch one 16-row MFMA tile:
+//   forward  Z1 = X W1^T on f32 MFMA 16x16x4, X staged MLP_KT features at a time (rows MLP_KS floats apart: the 16
+//            rows of an A operand fall into 16 different bank groups).  Within a tile the 4 waves split K and every
+//            wave feeds all NCT column tiles from one A operand read (a split by column tile would leave three waves
+//            idle at H = 16); the accumulators stay in registers across the tiles.  The same A register as A and B
+//            gives the Gram X X^T of the minibatch rows: one more MFMA per k step, no more LDS reads
+//   middle   h = relu(Z1 + b1), logits (K = H, wave 0), the loss rows (K1's CrossEntropyLoss), dW2 = G^T h and
+//            dH = (G W2) masked by h > 0 (column tile j on wave j), db1, db2: all in LDS and registers; the raw small
+//            gradient [db1 | dW2 | db2] waits in LDS for the clip
+//   clip     ||dW1||_F^2 = sum_st (dH dH^T)_st (X X^T)_st, one (s, t) term per thread, combined in fp64 in a fixed
+//            order with the small part's squares: the coefficient is known before dW1 exists
+//   dW1      = dH^T X (M = hidden units, N = k tile, K = samples): the tiles of X are staged again (the last one is
+//            still resident: it goes first), each output entry is scaled, quantised and stored once by the lane
+//            that finished it.  No H x D_IN accumulator lives across a barrier and delta is written once
+// LDS, all static (bytes): 17664 tile + 4096 NCT forward partials + 4096 Gram partials + 192 (H + 1) of h, dH, W2
+// + 68 H + 64 small gradient + 2048 logits and G + 296 = 32616 / 40872 / 49128 / 57384 at H = 16 / 32 / 48 / 64
+// (the compiler's figures): inside the default 64 KiB, no attribute is set at launch.
+// No atomics, no reduction whose order depends on timing: two runs give the same bytes.
+// =====================================================================================
+constexpr int MLP_KT = 256;          // == the block: one thread per staged column
+constexpr int MLP_KS = MLP_KT + 20;
+
+namespace {
+// rows rowidx[0, 16) of X (< 0: a zero row), features [k0, k0 + kw), as (x - tsub) * tmul
+__device__ __forceinline__ void mlp_stage(float* xs, const float* X, const long long* rowidx, int D_IN, int k0, int kw,
+                                          float tsub, float tmul) {
+  const int k = threadIdx.x;
+  if (k < kw) {
+#pragma unroll 4
+    for (int s = 0; s < 16; ++s) {
+      const long long r = rowidx[s];
+      xs[s * MLP_KS + k] = r >= 0 ? (X[r * (long long)D_IN + k0 + k] - tsub) * tmul : 0.f;
+    }
+  }
+}
+
+// the staged tile's share of Z1 = X W1^T (and of X X^T), this wave's quarter of the tile's k steps
+template <int NCT, bool GRAM>
+__device__ __forceinline__ void mlp_hidden_tile(const float* xs, const double* W1, int D_IN, int k0, int kw,
+                                                f32x4 (&acc)[NCT], f32x4& accg) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, i = lane & 15, kk = lane >> 4;
+  const int ksteps = (kw + 3) / 4, per = (ksteps + 3) / 4;
+  const int st1 = min(ksteps, (wid + 1) * per);
+#pragma unroll 2
+  for (int st = wid * per; st < st1; ++st) {
+    const int k = st * 4 + kk;
+    const bool in = k < kw;
+    const float av = in ? xs[i * MLP_KS + k] : 0.f;
+    float bv[NCT];
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) bv[j] = in ? (float)W1[(size_t)(j * 16 + i) * D_IN + k0 + k] : 0.f;
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[j], acc[j], 0, 0, 0);
+    if (GRAM) accg = __builtin_amdgcn_mfma_f32_16x16x4f32(av, av, accg, 0, 0, 0);
+  }
+}
+
+// Z1 over every tile of D_IN as four per-wave partials in red (and the Gram's in redg); the last tile stays in xs
+template <int NCT, bool GRAM>
+__device__ __forceinline__ void mlp_hidden_partials(float* xs, float (&red)[4][NCT][16][16], float (*redg)[16][16],
+                                                    const float* X, const long long* rowidx, const double* W1,
+                                                    int D_IN, float tsub, float tmul) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  f32x4 acc[NCT], accg = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < NCT; ++j) acc[j] = accg;
+  const int ktiles = (D_IN + MLP_KT - 1) / MLP_KT;
+  for (int kt = 0; kt < ktiles; ++kt) {
+    const int k0 = kt * MLP_KT, kw = min(MLP_KT, D_IN - k0);
+    if (kt > 0) __syncthreads();  // the previous tile has been consumed
+    mlp_stage(xs, X, rowidx, D_IN, k0, kw, tsub, tmul);
+    __syncthreads();
+    mlp_hidden_tile<NCT, GRAM>(xs, W1, D_IN, k0, kw, acc, accg);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) red[wid][j][(lane >> 4) * 4 + r][lane & 15] = acc[j][r];
+    if (GRAM) redg[wid][(lane >> 4) * 4 + r][lane & 15] = accg[r];
+  }
+  __syncthreads();
+}
+
+// h[s][u] = relu(Z1[s][u] + b1[u]) on rows s < rows, 0 on the others
+template <int NCT>
+__device__ __forceinline__ void mlp_hidden_relu(const float (&red)[4][NCT][16][16], const double* b1, int rows,
+                                                float (&hs)[16][NCT * 16 + 1]) {
+  constexpr int H = NCT * 16;
+  for (int e = threadIdx.x; e < 16 * H; e += 256) {
+    const int s = e / H, u = e % H, j = u >> 4, c = u & 15;
+    const float z = (red[0][j][s][c] + red[1][j][s][c]) + (red[2][j][s][c] + red[3][j][s][c]) + (float)b1[u];
+    hs[s][u] = (s < rows && z > 0.f) ? z : 0.f;
+  }
+  __syncthreads();
+}
+}  // namespace
+
+template <int NCT>
+__global__ void __launch_bounds__(256) k_mlp_step(const float* X, const int* y, const long long* off, const int* ntrain,
+                                                  const int* pid, const double* W, int D_IN, int D_OUT, int B, int P,
+                                                  unsigned long long seed, int iteration, float max_norm, double qscale,
+                                                  float* delta, long long* qdelta, float* loss, int lo) {
+  constexpr int H = NCT * 16;
+  __shared__ float xs[16 * MLP_KS];     // minibatch rows, transformed; rows >= Bq are zero
+  __shared__ float red[4][NCT][16][16];  // per-wave partials of Z1
+  __shared__ float redg[4][16][16];     // per-wave partials of X X^T
+  __shared__ float hs[16][H + 1];       // relu(Z1 + b1)
+  __shared__ float dh[16][H + 1];       // d(mean loss) / d(Z1)
+  __shared__ float w2s[16][H + 1];      // (float)W2, rows >= D_OUT zero
+  __shared__ float lg[16][16];
+  __shared__ float G[16][16];           // d(mean loss) / d(logits)
+  __shared__ float gs[H + 16 * H + 16];  // the raw [db1 | dW2 | db2]
+  __shared__ float rowloss[16];
+  __shared__ long long rowidx[16];
+  __shared__ int bidx[16];
+  __shared__ double nrm[4];
+  __shared__ float scale_sh;
+  const int p = blockIdx.x;
+  if (p >= P) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i = lane & 15, kk = lane >> 4;
+  const double *b1 = W + (size_t)H * D_IN, *W2 = b1 + H, *b2 = W2 + D_OUT * H;
+  const int nsmall = H + D_OUT * H + D_OUT;
+  const size_t nparam = (size_t)H * D_IN + nsmall;
+  const int li = lo >= 0 ? pid[p] - lo : p;
+  const long long offp = off[li];
+  const int n = ntrain[li];
+  // 1. K1's draw: B distinct minibatch indices from the same Philox counters
+  if (tid == 0) {
+    int cnt = 0;
+    uint32_t ctr = 0;
+    while (cnt < B && cnt < n) {
+      u4 r = philox(u4{(uint32_t)pid[p], (uint32_t)iteration, ctr++, 0x5EEDu}, (uint32_t)seed, (uint32_t)(seed >> 32));
+      const uint32_t cand[4] = {r.x, r.y, r.z, r.w};
+      for (int q = 0; q < 4 && cnt < B && cnt < n; ++q) {
+        const int c = (int)(cand[q] % (uint32_t)n);
+        bool dup = false;
+        for (int t = 0; t < cnt; ++t) dup |= bidx[t] == c;
+        if (!dup) bidx[cnt++] = c;
+      }
+    }
+    for (int t = 0; t < 16; ++t) rowidx[t] = t < cnt ? offp + bidx[t] : -1;
+  }
+  for (int e = tid; e < 16 * H; e += 256) w2s[e / H][e % H] = e / H < D_OUT ? (float)W2[e] : 0.f;
+  __syncthreads();
+  const int Bq = min(B, n);
+  // 2. forward: Z1 (+ the Gram of the rows), h
+  mlp_hidden_partials<NCT, true>(xs, red, redg, X, rowidx, W, D_IN, 0.5f, 2.0f);
+  mlp_hidden_relu<NCT>(red, b1, Bq, hs);
+  // 3. logits = h W2^T (wave 0; b2 joins in the loss rows)
+  if (wid == 0) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int st = 0; st < H / 4; ++st)
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hs[i][st * 4 + kk], w2s[i][st * 4 + kk], acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lg[kk * 4 + r][i] = acc[r];
+  }
+  __syncthreads();
+  // 4. the loss and its gradient with respect to the logits on rows s < Bq (one thread per row)
+  if (tid < 16) {
+    const int s = tid;
+    float l = 0.f;
+    if (s < Bq) {
+      float lr[16];
+      for (int c = 0; c < D_OUT; ++c) lr[c] = lg[s][c] + (float)b2[c];
+      l = CrossEntropyLoss::row(lr, D_OUT, y[rowidx[s]], Bq, G[s]);
+      for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
+    } else {
+      for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
+    }
+    rowloss[s] = l;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float l = 0.f;
+    for (int s = 0; s < Bq; ++s) l += rowloss[s];
+    loss[p] = l / (float)max(Bq, 1);
+  }
+  // 5. column tile j on wave j: dW2[c][u] = sum_s G[s][c] h[s][u] (M = classes, K = samples) and
+  // dH[s][u] = sum_c G[s][c] W2[c][u] where h[s][u] > 0 (M = samples, K = classes)
+  for (int j = wid; j < NCT; j += 4) {
+    f32x4 accw = {0.f, 0.f, 0.f, 0.f}, acch = {0.f, 0.f, 0.f, 0.f};
+    const int u = j * 16 + i;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int q = ks * 4 + kk;
+      accw = __builtin_amdgcn_mfma_f32_16x16x4f32(G[q][i], hs[q][u], accw, 0, 0, 0);
+      acch = __builtin_amdgcn_mfma_f32_16x16x4f32(G[i][q], w2s[q][u], acch, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = kk * 4 + r;   // the class of accw's row, the sample of acch's
+      if (q < D_OUT) gs[H + q * H + u] = accw[r];
+      dh[q][u] = hs[q][u] > 0.f ? acch[r] : 0.f;
+    }
+  }
+  if (tid < D_OUT) {
+    float db = 0.f;
+    for (int s = 0; s < 16; ++s) db += G[s][tid];
+    gs[H + D_OUT * H + tid] = db;
+  }
+  __syncthreads();
+  if (tid < H) {
+    float db = 0.f;
+    for (int s = 0; s < 16; ++s) db += dh[s][tid];
+    gs[tid] = db;
+  }
+  // 6. clip_grad_norm(max_norm) over all four parameter blocks, before dW1 exists
+  double part;
+  {
+    const int s = tid >> 4, t = tid & 15;
+    float dd = 0.f;
+    for (int u = 0; u < H; ++u) dd += dh[s][u] * dh[t][u];
+    const float xx = (redg[0][s][t] + redg[1][s][t]) + (redg[2][s][t] + redg[3][s][t]);
+    part = (double)dd * (double)xx;
+  }
+  __syncthreads();
+  for (int e = tid; e < nsmall; e += 256) part += (double)gs[e] * (double)gs[e];
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+  if (lane == 0) nrm[wid] = part;
+  __syncthreads();
+  if (tid == 0) {
+    const float tot = sqrtf((float)fmax((nrm[0] + nrm[1]) + (nrm[2] + nrm[3]), 0.0));
+    const float coef = max_norm / (tot + 1e-6f);
+    scale_sh = coef < 1.f ? coef : 1.f;
+  }
+  __syncthreads();
+  // 7. delta = -clipped gradient, quantised like updateFloatToInt: the small blocks, then dW1 tile by tile
+  const float sc = -scale_sh;
+  float* dst = delta + (size_t)p * nparam;
+  long long* qd = qdelta + (size_t)p * nparam;
+  for (int e = tid; e < nsmall; e += 256) {
+    const float v = gs[e] * sc;
+    dst[(size_t)H * D_IN + e] = v;
+    qd[(size_t)H * D_IN + e] = quantize(v, qscale);
+  }
+  float ah[NCT][4];   // A[u][s] of dW1 = dH^T X, every column tile
+#pragma unroll
+  for (int j = 0; j < NCT; ++j)
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) ah[j][ks] = dh[ks * 4 + kk][j * 16 + i];
+  const int ktiles = (D_IN + MLP_KT - 1) / MLP_KT;
+  for (int q = 0; q < ktiles; ++q) {
+    const int kt = (ktiles - 1 + q) % ktiles;
+    const int k0 = kt * MLP_KT, kw = min(MLP_KT, D_IN - k0);
+    if (q > 0) {
+      __syncthreads();
+      mlp_stage(xs, X, rowidx, D_IN, k0, kw, 0.5f, 2.0f);
+      __syncthreads();
+    }
+    const int ntiles = (kw + 15) / 16;
+    for (int t = wid; t < ntiles; t += 4) {
+      const int k = t * 16 + i;
+      const bool in = k < kw;
+      float bx[4];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) bx[ks] = in ? xs[(ks * 4 + kk) * MLP_KS + k] : 0.f;
+#pragma unroll
+      for (int j = 0; j < NCT; ++j) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ah[j][ks], bx[ks], acc, 0, 0, 0);
+        if (in) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const size_t e = (size_t)(j * 16 + kk * 4 + r) * D_IN + k0 + k;
+            const float v = acc[r] * sc;
+            dst[e] = v;
+            qd[e] = quantize(v, qscale);
+          }
+        }
+      }
+    }
+  }
 }
 
 // =====================================================================================
@@ -2200,6 +2482,61 @@ extern "C" __global__ void __launch_bounds__(64) k_eval_finish(unsigned int* err
   }
 }
 
+// K2m: the same two miss counts for K1m's MLP (W in its layout).  One block per 16-row tile, on the step's forward:
+// each feature of the tile's rows is staged once, MLP_KT at a time with the transform fused, the 4 waves split
+// the k steps of a staged tile and feed all NCT column tiles; h = relu(Z1 + b1) stays in LDS and wave 0 takes it
+// through the second layer (K = H, W2 from L2) to the argmax across the 16 class lanes (first maximum) and the
+// compare against y: one integer atomic per (four rows, set) that missed.  LDS: 17664 + 4096 NCT + 64 (H + 1) + 128 bytes.
+template <int NCT>
+__global__ void __launch_bounds__(256) k_mlp_eval(const float* X, const int* y, int N, int D_IN, int D_OUT,
+                                                  const double* W, int transform, int split, unsigned int* err) {
+  constexpr int H = NCT * 16;
+  __shared__ float xs[16 * MLP_KS];
+  __shared__ float red[4][NCT][16][16];
+  __shared__ float hs[16][H + 1];
+  __shared__ long long rowidx[16];
+  const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, kk = lane >> 4;
+  const int row0 = blockIdx.x * 16;
+  if (tid < 16) rowidx[tid] = row0 + tid < N ? row0 + tid : -1;
+  __syncthreads();
+  const double *b1 = W + (size_t)H * D_IN, *W2 = b1 + H, *b2 = W2 + D_OUT * H;
+  mlp_hidden_partials<NCT, false>(xs, red, nullptr, X, rowidx, W, D_IN, transform ? 0.5f : 0.f, transform ? 2.f : 1.f);
+  mlp_hidden_relu<NCT>(red, b1, 16, hs);
+  if (tid >= 64) return;
+  const bool cval = i < D_OUT;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int st = 0; st < H / 4; ++st) {
+    const float bv = cval ? (float)W2[i * H + st * 4 + kk] : 0.f;
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hs[i][st * 4 + kk], bv, acc, 0, 0, 0);
+  }
+  const float bias = cval ? (float)b2[i] : 0.f;
+  unsigned int cnt0 = 0, cnt1 = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {   // lane holds the logit of row kk * 4 + r, class i
+    float bv = cval ? acc[r] + bias : -__builtin_huge_valf();
+    int bc = i;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 16);
+      const int oc = __shfl_xor(bc, o, 16);
+      if (ov > bv || (ov == bv && oc < bc)) {
+        bv = ov;
+        bc = oc;
+      }
+    }
+    const int row = row0 + kk * 4 + r;
+    if (i == 0 && row < N && bc != y[row]) {
+      if (row < split) ++cnt0;
+      else ++cnt1;
+    }
+  }
+  if (i == 0) {
+    if (cnt0) atomicAdd(err, cnt0);
+    if (cnt1) atomicAdd(err + 1, cnt1);
+  }
+}
+
 // =====================================================================================
 // Committee RONI (VerifyUpdateRONI, main.go:191-233): every local verifier's minibatch scored under the base
 // model and under W + U[c] for every row c of its inbox, in ONE launch.  counts[v][0] = #misclassified
@@ -2611,6 +2948,27 @@ extern "C" int bsc_margin_step(const float* X, const int* y, const long long* of
   return (int)hipGetLastError();
 }
 
+// K1m: bsc_softmax_step's arguments and limits with H hidden units in front of D_OUT (a multiple of 16 up to 64)
+// and W in the MLP's layout; no speculative row flags (the ledger does not run this model)
+extern "C" int bsc_mlp_step(const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,
+                            const double* W, int D_IN, int H, int D_OUT, int B, int P, unsigned long long seed,
+                            int iteration, float max_norm, double qscale, float* delta, long long* qdelta, float* loss,
+                            int lo, void* stream) {
+  if (D_IN <= 0 || D_OUT < 1 || D_OUT > 16 || B > 16 || H < 16 || H > 64 || H % 16 != 0) return -1;
+  if (P <= 0) return 0;
+#define BSC_MLP_STEP(NCT)                                                                                            \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mlp_step<NCT>), dim3(P), dim3(256), 0, (hipStream_t)stream, X, y, off, ntrain, \
+                     pid, W, D_IN, D_OUT, B, P, seed, iteration, max_norm, qscale, delta, qdelta, loss, lo)
+  switch (H / 16) {
+    case 1: BSC_MLP_STEP(1); break;
+    case 2: BSC_MLP_STEP(2); break;
+    case 3: BSC_MLP_STEP(3); break;
+    default: BSC_MLP_STEP(4); break;
+  }
+#undef BSC_MLP_STEP
+  return (int)hipGetLastError();
+}
+
 namespace {
 template <class Loss>
 int local_steps_launch(hipStream_t s, int nparam, const float* X, const int* y, const long long* off, const int* ntrain,
@@ -2969,6 +3327,26 @@ extern "C" int bsc_eval_error_t_rb(const float* Xt, const int* y, int N, int KG,
   // err: 3 zeroed counters; k_eval_finish writes err_host and re-zeroes them
   hipLaunchKernelGGL(k_eval_error_t, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream, Xt, y, N, KG, D_IN, D_OUT,
                      W, split, err, err_host);
+  hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, err, err_host);
+  return (int)hipGetLastError();
+}
+
+// K2m with bsc_eval_error_t_rb's hand-off: err holds 3 zeroed counters, k_eval_finish writes err_host and re-zeroes them
+extern "C" int bsc_mlp_eval_rb(const float* X, const int* y, int N, int D_IN, int H, int D_OUT, const double* W,
+                               int transform, int split, unsigned int* err, unsigned int* err_host, void* stream) {
+  if (D_IN <= 0 || D_OUT < 1 || D_OUT > 16 || H < 16 || H > 64 || H % 16 != 0) return -1;
+  if (N > 0) {
+#define BSC_MLP_EVAL(NCT)                                                                                           \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mlp_eval<NCT>), dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream, X, y, \
+                     N, D_IN, D_OUT, W, transform, split, err)
+    switch (H / 16) {
+      case 1: BSC_MLP_EVAL(1); break;
+      case 2: BSC_MLP_EVAL(2); break;
+      case 3: BSC_MLP_EVAL(3); break;
+      default: BSC_MLP_EVAL(4); break;
+    }
+#undef BSC_MLP_EVAL
+  }
   hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, err, err_host);
   return (int)hipGetLastError();
 }

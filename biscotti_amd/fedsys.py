@@ -21,9 +21,12 @@ def build_parser() -> argparse.ArgumentParser:
     add_framework_flags(ap)
     ap.set_defaults(perc_samples=35, epsilon=5.0)
     ap.add_argument("--rounds", type=int, default=None)
-    ap.add_argument("--model", default="softmax", choices=["softmax", "svm"],
-                    help="softmax regression, or svm: the same linear scorer under the multi-class margin loss "
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp"],
+                    help="softmax regression, svm: the same linear scorer under the multi-class margin loss, or mlp: a "
+                         "one-hidden-layer ReLU MLP under cross-entropy (k_mlp_step; the plain single step only) "
                          "(mnist and lfw)")
+    ap.add_argument("--mlp-hidden", type=int, default=32, metavar="H",
+                    help="hidden units of --model mlp: a multiple of 16 in 16..64")
     ap.add_argument("--topk", type=float, default=1.0, metavar="THETA",
                     help="top-k sparsified updates: every worker keeps the int(d * THETA) largest-magnitude entries "
                          "of its update (mnist and lfw, 0 < THETA <= 1, 1 = off)")
@@ -71,7 +74,7 @@ def main(argv=None) -> int:
     comm = Comm.init(device=cfg.device)
     eng = FedSysEngine(cfg, comm, model=ns.model, topk=ns.topk, local_steps=ns.local_steps, local_lr=ns.local_lr,
                        dp_clip=ns.dp_clip, dp_sigma=ns.dp_sigma, lot_size=ns.lot_size, local_momentum=ns.local_momentum,
-                       local_decay=ns.local_decay, local_prox=ns.local_prox)
+                       local_decay=ns.local_decay, local_prox=ns.local_prox, hidden=ns.mlp_hidden)
     n = 0
     while ns.rounds is None or n < ns.rounds:
         if eng.run_round() is None:

@@ -201,6 +201,42 @@ class SoftmaxTask:
         return rows, nrows
 
 
+class MlpTask(SoftmaxTask):
+    """SoftmaxTask's data under a one-hidden-layer ReLU MLP of `hidden` units (K.mlp_step / K.mlp_errors_async;
+    docs/QUIRKS.md Q21).  FedSys only: the ledger's d, pre-step, RONI and genesis model are the linear scorer's."""
+
+    def __init__(self, peers: range, num_peers: int, device, seed: int, hidden: int = 32, **kw):
+        super().__init__(peers, num_peers, device, seed, **kw)
+        self.hidden = int(hidden)
+        self.nparam = K.mlp_nparam(self.d_in, self.hidden, self.d_out)   # raises on a width the kernels do not take
+
+    def initial_model(self) -> torch.Tensor:
+        """The model of round 0, the same on every rank (K.mlp_init under the run's seed)."""
+        return K.mlp_init(self.d_in, self.hidden, self.d_out, self.seed).to(self.device)
+
+    def step(self, W: torch.Tensor, iteration: int, peers: list[int]):
+        if not peers:
+            z = torch.empty((0, self.nparam), device=self.device)
+            return z.float(), z.long()
+        pid = h2d(peers, torch.int32, self.device)
+        delta, qdelta, self.last_loss = K.mlp_step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in,
+                                                   self.hidden, self.d_out, self.batch, self.seed, iteration, 100.0,
+                                                   1e4, lo=self.peers[0])
+        return delta, qdelta
+
+    def evaluate_async(self, W: torch.Tensor):
+        both = K.mlp_errors_async(self.eval_X, self.eval_y, self.eval_split, W, self.d_in, self.hidden, self.d_out)
+
+        def result():
+            err, att = both()
+            return {"test_error": err, "attack_rate": att}
+        result.ready = both.ready
+        return result
+
+    def train_error(self, W: torch.Tensor, peer: int, iteration: int) -> float:
+        raise NotImplementedError("RONI scores the ledger's linear models; the MLP runs under FedSys only")
+
+
 class LogisticTask:
     """creditcard logistic regression: every peer loads the full dataset (logistic_model.py:26)."""
 
@@ -324,17 +360,39 @@ class LogisticTask:
 MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 
+def ledger_model(model: str) -> str:
+    """`model` for a ledger engine or tool: the MLP has no place there yet."""
+    if model == "mlp":
+        raise ValueError("model 'mlp': FedSys only for now: the ledger's d, pre-step and genesis model are linear")
+    return model
+
+
 def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, model: str = "softmax",
               topk: float = 1.0, local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0,
               dp_sigma: float = 0.0, lot_size: int = 0, local_momentum: float = 0.0, local_decay: float = 0.0,
-              local_prox: float = 0.0, **kw):
+              local_prox: float = 0.0, hidden: int = 32, **kw):
     """The dataset's task.  model "svm" trains mnist / lfw's linear scorer under the margin loss (SoftmaxTask with
     loss="margin"); creditcard has its logistic model only.  topk < 1: mnist / lfw's peers send top-k sparsified
     updates (SoftmaxTask's topk).  local_steps > 1: they run that many local SGD steps per round at rate local_lr
     (SoftmaxTask's local_steps).  dp_clip > 0: their steps are DP-SGD steps, per-example clip dp_clip and noise
     multiplier dp_sigma (SoftmaxTask's dp_clip).  lot_size > 0: every step draws lot_size examples, up to 256, in
     place of batch_size (SoftmaxTask's lot_size).  local_momentum / local_decay / local_prox > 0: the local steps run
-    under heavy-ball momentum, weight decay and a FedProx proximal weight (SoftmaxTask's local_momentum)."""
+    under heavy-ball momentum, weight decay and a FedProx proximal weight (SoftmaxTask's local_momentum).
+    model "mlp" (FedSys only, not one of MODELS): mnist / lfw under a one-hidden-layer ReLU MLP of `hidden` units
+    (MlpTask), the plain single step only."""
+    if model == "mlp":
+        if dataset not in ("mnist", "lfw"):
+            raise ValueError("model 'mlp' needs a multi-class dataset (mnist, lfw): creditcard trains its logistic model")
+        if topk != 1.0 or local_steps != 1 or local_lr != 1.0 or dp_clip != 0 or dp_sigma != 0 or lot_size != 0 or \
+                local_momentum != 0 or local_decay != 0 or local_prox != 0:
+            raise ValueError("model 'mlp' takes the plain single step: topk, local_steps / local_lr, dp_clip / dp_sigma, "
+                             "lot_size and local_momentum / local_decay / local_prox are kernels of the linear scorer only")
+        for k in ("epsilon", "colluders") + (("data_dir",) if dataset == "lfw" else ()):
+            kw.pop(k, None)
+        if dataset == "lfw":
+            _, d_in, d_out = D.dataset_dims("lfw")
+            kw.update(federation=D.lfw_federation(num_peers, seed=seed), dims=(d_in, d_out))
+        return MlpTask(peers, num_peers, device, seed, hidden=hidden, **kw)
     if model not in MODELS:
         raise ValueError(f"unsupported model {model!r} (one of {', '.join(MODELS)})")
     if model == "svm" and dataset == "creditcard":

@@ -189,6 +189,119 @@ def margin_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_
     return _linear_step("margin_step", X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm, qscale, lo)
 
 
+# ---------------------------------------------------------------------------- K1m / K2m one-hidden-layer MLP
+def _mlp_check(H: int, d_out: int) -> None:
+    if H != int(H) or not 16 <= H <= 64 or H % 16:
+        raise ValueError(f"the MLP's hidden width is a multiple of 16 in 16..64, not {H!r}")
+    if not 1 <= d_out <= 16:
+        raise ValueError(f"the MLP kernels take up to 16 classes, not {d_out!r}")
+
+
+def mlp_nparam(d_in: int, H: int, d_out: int) -> int:
+    """Parameters of the d_in -> H -> d_out MLP; ValueError on a shape k_mlp_step does not take."""
+    _mlp_check(H, d_out)
+    return H * d_in + H + d_out * H + d_out
+
+
+def _mlp_split(Wm, d_in, H, d_out):
+    """[W1 (H x d_in) | b1 (H) | W2 (d_out x H) | b2 (d_out)]: nn.Sequential(Linear, ReLU, Linear).parameters()."""
+    a, b, c = H * d_in, H * d_in + H, H * d_in + H + d_out * H
+    return Wm[:a].view(H, d_in), Wm[a:b], Wm[b:c].view(d_out, H), Wm[c:]
+
+
+def mlp_init(d_in: int, H: int, d_out: int, seed: int) -> torch.Tensor:
+    """The MLP's initial vector, fp64 on the host: He-uniform weights (bound sqrt(6 / fan_in)) from the Philox stream
+    of tag 0x1417 under `seed`, zero biases.  A function of its arguments only: the same on every rank.  (All-zero
+    weights are a fixed point of this model: no gradient reaches W1 through W2 = 0, nor W2 through h = 0.)"""
+    _mlp_check(H, d_out)
+    n = H * d_in + d_out * H
+    r = philox4x32(np.arange((n + 3) // 4), 0, 0, 0x1417, seed & MASK32, (seed >> 32) & MASK32)
+    u = ((np.stack(r, 1).reshape(-1)[:n] >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0 * 2.0 - 1.0
+    W = np.zeros(mlp_nparam(d_in, H, d_out))
+    W[: H * d_in] = u[: H * d_in] * math.sqrt(6.0 / d_in)
+    W[H * d_in + H: H * d_in + H + d_out * H] = u[H * d_in:] * math.sqrt(6.0 / H)
+    return torch.from_numpy(W)
+
+
+def mlp_step(X, y, off, ntrain, pid, W, d_in, H, d_out, B, seed, iteration, max_norm=100.0, qscale=1e4, lo=-1):
+    """softmax_step for the one-hidden-layer MLP x -> relu(W1 x + b1) -> W2 h + b2 under cross-entropy (k_mlp_step):
+    the same minibatch draw, transform, clip of the whole gradient and quantisation.  W fp64 [mlp_nparam], laid out
+    as _mlp_split reads it; H a multiple of 16 in 16..64.  The other arguments and the return values are
+    softmax_step's."""
+    _mlp_check(H, d_out)
+    P = pid.numel()
+    nparam = mlp_nparam(d_in, H, d_out)
+    dev = X.device
+    delta = torch.empty((P, nparam), dtype=torch.float32, device=dev)
+    qdelta = torch.empty((P, nparam), dtype=torch.int64, device=dev)
+    loss = torch.empty((P,), dtype=torch.float32, device=dev)
+    if dev.type == "cuda":
+        assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+        assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
+        assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P)
+        _check(hip().bsc_mlp_step(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), d_in, H, d_out, B, P,
+                                  seed & (2**64 - 1), iteration, float(max_norm), float(qscale), _p(delta), _p(qdelta),
+                                  _p(loss), int(lo), _stream()), "mlp_step")
+        return delta, qdelta, loss
+    W1, b1, W2, b2 = _mlp_split(W.to(torch.float32), d_in, H, d_out)
+    pids = pid.tolist()
+    if lo >= 0:
+        offs = [int(off[q - lo]) for q in pids]
+        ns = [int(ntrain[q - lo]) for q in pids]
+    else:
+        offs, ns = off.tolist(), ntrain.tolist()
+    for p in range(P):
+        idx = minibatch_indices(pids[p], iteration, ns[p], B, seed)
+        rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
+        xb = (X[rows] - 0.5) / 0.5
+        z1 = xb @ W1.T + b1
+        h = torch.relu(z1)
+        lossv, g = _ce_rows(h @ W2.T + b2, y[rows].long())
+        dh = (g @ W2) * (z1 > 0)
+        flat = torch.cat([(dh.T @ xb).reshape(-1), dh.sum(0), (g.T @ h).reshape(-1), g.sum(0)])
+        coef = max_norm / (float(torch.linalg.vector_norm(flat)) + 1e-6)
+        if coef < 1:
+            flat = flat * coef
+        delta[p] = -flat
+        qdelta[p] = torch.from_numpy((delta[p].double().numpy() * qscale).astype(np.int64))
+        loss[p] = lossv
+    return delta, qdelta, loss
+
+
+def mlp_errors_async(X, y, split: int, W, d_in, H, d_out, transform=True):
+    """eval_errors_async for the MLP (k_mlp_eval): the error rates of W on rows [0, split) and [split, N) of X from
+    one launch and one read-back.  Returns a callable giving (err_a, err_b), with .ready like eval_errors_async's."""
+    _mlp_check(H, d_out)
+    N = X.shape[0]
+    na, nb = split, N - split
+    if X.device.type != "cuda":
+        W1, b1, W2, b2 = _mlp_split(W.to(torch.float32), d_in, H, d_out)
+        xb = (X - 0.5) / 0.5 if transform else X
+        miss = torch.argmax(torch.relu(xb @ W1.T + b1) @ W2.T + b2, 1) != y.long()
+        e = (int(miss[:split].sum()), int(miss[split:].sum()))
+        ready = lambda: True   # noqa: E731
+    else:
+        assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+        assert W.numel() == mlp_nparam(d_in, H, d_out) and 0 <= split <= N
+        host = pinned("mlp_eval", (2,), torch.int32, depth=4)
+        err = _EVAL_DEV.get((host.data_ptr(), "mlp"))   # 3 counters, zero between launches (k_eval_finish)
+        if err is None:
+            err = _EVAL_DEV[(host.data_ptr(), "mlp")] = torch.zeros((4,), dtype=torch.int32, device=X.device)
+        _check(hip().bsc_mlp_eval_rb(_p(X), _p(y), N, d_in, H, d_out, _p(W), int(transform), int(split), _p(err),
+                                     host.data_ptr(), _stream()), "mlp_eval")
+        ev = S.record()
+        e, ready = None, ev.query
+
+    def result():
+        c = e
+        if c is None:
+            S.host_wait(ev)
+            c = host.tolist()
+        return (c[0] / na if na else 0.0, c[1] / nb if nb else 0.0)
+    result.ready = ready
+    return result
+
+
 def local_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, E, lr, loss="ce", max_norm=100.0,
                 qscale=1e4, lo=-1):
     """E local SGD steps per peer at rate lr under loss "ce" or "margin" (k_local_steps): step e differentiates the

@@ -82,8 +82,11 @@ class BiscottiEngine(RoundHeadMixin, VerifyMixin, SecAggMixin, KzgAuditMixin, Vr
                  local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0,
                  lot_size: int = 0,
                  local_momentum: float = 0.0, local_decay: float = 0.0, local_prox: float = 0.0):
+        from ..models.tasks import ledger_model
+
         cfg.validate()
         self.cfg = cfg
+        ledger_model(model)
         # the ledger's model ("softmax", or "svm": the same scorer under the margin loss; models.make_task).  An
         # engine switch like sign_device, not a RunConfig field; a chain does not record it: a resumed run must
         # be given the same one

@@ -48,12 +48,14 @@ class FedSysEngine:
     def __init__(self, cfg: RunConfig, comm: Comm | None = None, *, model: str = "softmax", topk: float = 1.0,
                  local_steps: int = 1, local_lr: float = 1.0, dp_clip: float = 0.0, dp_sigma: float = 0.0,
                  lot_size: int = 0,
-                 local_momentum: float = 0.0, local_decay: float = 0.0, local_prox: float = 0.0):
+                 local_momentum: float = 0.0, local_decay: float = 0.0, local_prox: float = 0.0, hidden: int = 32):
         from ..data import dataset_dims
         from ..models import make_task
 
         self.cfg = cfg
-        self.model = model   # "softmax" or "svm" (models.make_task), as BiscottiEngine's
+        # "softmax" or "svm" (models.make_task), as BiscottiEngine's; here also "mlp", a one-hidden-layer ReLU MLP of
+        # `hidden` units (docs/QUIRKS.md Q21)
+        self.model, self.hidden = model, hidden
         self.topk = topk     # top-k sparsified updates (models.make_task), as BiscottiEngine's; 1: off
         self.local_steps, self.local_lr = local_steps, local_lr   # local SGD steps per round and their rate; 1: off
         self.dp_clip, self.dp_sigma = dp_clip, dp_sigma           # DP-SGD's per-example clip and noise multiplier; 0: off
@@ -77,16 +79,18 @@ class FedSysEngine:
         fc.derive()
         self.fc = fc
         pc = cfg.protocol(self.R)
-        self.d = dataset_dims(cfg.dataset)[0]
-        probe = self.R.RoundFSM(pc, self.d)
+        probe = self.R.RoundFSM(pc, dataset_dims(cfg.dataset)[0])
         poisoned = {p for p in self.local if probe.is_poisoner(p, True)}   # FedSys: >= (Q4)
         self.task = make_task(cfg.dataset, self.local, self.N, self.dev, cfg.seed, model=model, topk=topk,
                               local_steps=local_steps, local_lr=local_lr, dp_clip=dp_clip, dp_sigma=dp_sigma,
                               lot_size=lot_size, local_momentum=local_momentum, local_decay=local_decay,
-                              local_prox=local_prox, poisoned=poisoned, batch_size=cfg.batch_size, data_dir=cfg.data_dir,
-                              epsilon=cfg.epsilon, colluders=set())
+                              local_prox=local_prox, hidden=hidden, poisoned=poisoned, batch_size=cfg.batch_size,
+                              data_dir=cfg.data_dir, epsilon=cfg.epsilon, colluders=set())
+        self.d = self.task.nparam
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
-        self.W = torch.zeros(self.d, dtype=torch.float64, device=self.dev)
+        # a task whose all-zero model cannot train (the MLP) brings its own round-0 model, the same on every rank
+        init = getattr(self.task, "initial_model", None)
+        self.W = init() if init else torch.zeros(self.d, dtype=torch.float64, device=self.dev)
         self.iteration = 0
         self.history: list = []        # BlockData of every model the server broadcast
 

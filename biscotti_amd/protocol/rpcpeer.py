@@ -44,8 +44,10 @@ class RpcPeer:
                  local_prox: float = 0.0):
         from ..data import dataset_dims
         from ..models import make_task
+        from ..models.tasks import ledger_model
         from .engine import _seed_bytes
 
+        ledger_model(model)
         R = self.R = rt()
         self.cfg, self.id, self.addrs, self.timeout = cfg, int(peer_id), list(addresses), timeout_s
         self.N = cfg.num_nodes

@@ -2,6 +2,7 @@
 
     python -m biscotti_amd.sandbox --model softmax --dataset mnist --clients 10 --poisoned 4
     python -m biscotti_amd.sandbox --model svm --loss margin             # svm_model.py under the margin criterion
+    python -m biscotti_amd.sandbox --model mlp --mlp-hidden 32           # the project's MLP kernels (k_mlp_step)
     python -m biscotti_amd.sandbox --model mnist_cnn --iters 500
     python -m biscotti_amd.sandbox --model cifar_cnn --dataset cifar
     python -m biscotti_amd.sandbox --model lfw_cnn --dataset lfw
@@ -61,8 +62,56 @@ def _model(name: str, d_in: int, n_classes: int):
             "cifar_cnn": Z.CIFARCNNModel}[name]()
 
 
+def _run_mlp(dataset, clients, poisoned, iters, batch, lr, momentum, weight_decay, eval_every, seed, dev, verbose,
+             hidden) -> dict:
+    """--model mlp: the reference loop on the project's own MLP ops instead of a torch module -- every client's
+    minibatch gradient from one K.mlp_step launch (k_mlp_step on a GPU; its Philox draw, its (x - 0.5) / 0.5 transform
+    and client.py's clip at 100), summed, one SGD step on the flat vector, evaluation by K.mlp_errors_async."""
+    from .ops import ml as K
+
+    Xtr, ytr, Xte, yte, C = _data(dataset, seed)
+    honest = max(1, clients - poisoned)
+    shards = np.array_split(np.random.default_rng(seed).permutation(len(Xtr)), honest)
+    ones = np.nonzero(ytr == 1)[0]
+    rows = [shards[c] if c < honest else ones for c in range(clients)]
+    X = torch.from_numpy(np.concatenate([Xtr[r] for r in rows]).astype(np.float32)).to(dev)
+    y = torch.from_numpy(np.concatenate([ytr[r] if c < honest else np.full(len(r), 7 if C > 7 else 0)
+                                         for c, r in enumerate(rows)]).astype(np.int32)).to(dev)
+    ns = [len(r) for r in rows]
+    off = torch.tensor(np.cumsum([0] + ns[:-1]), dtype=torch.int64, device=dev)
+    nt = torch.tensor(ns, dtype=torch.int32, device=dev)
+    pid = torch.arange(clients, dtype=torch.int32, device=dev)
+    m1 = np.argsort(yte != 1, kind="stable")   # the 1s last: test error over all rows, attack rate over the 1s
+    n1 = int((yte == 1).sum())
+    eX = torch.from_numpy(np.concatenate([Xte, Xte[m1[:n1]]]).astype(np.float32)).to(dev)
+    ey = torch.from_numpy(np.concatenate([yte, yte[m1[:n1]]]).astype(np.int32)).to(dev)
+    d_in = Xtr.shape[1]
+    W = K.mlp_init(d_in, hidden, C, seed).to(dev)
+    vel = torch.zeros_like(W)
+    hist = []
+    for it in range(iters):
+        delta, _, loss = K.mlp_step(X, y, off, nt, pid, W, d_in, hidden, C, batch, seed, it)
+        vel = momentum * vel - delta.double().sum(0) + weight_decay * W   # delta = -clip(grad)
+        W = W - lr * vel
+        if it % eval_every == 0 or it == iters - 1:
+            err, att = K.mlp_errors_async(eX, ey, len(yte), W, d_in, hidden, C)()
+            hist.append({"iter": it, "loss": float(loss.mean()), "test_error": err,
+                         "attack_rate": att if n1 else float("nan")})
+            if verbose:
+                print(f"Average loss is {hist[-1]['loss']:.5f}\nTest error: {err:.5f}\nAttack rate on 1s: {att:.5f}\n")
+    return {"model": "mlp", "loss": "ce", "dataset": dataset, "final_test_error": hist[-1]["test_error"],
+            "final_attack_rate": hist[-1]["attack_rate"], "history": hist}
+
+
 def run(model="softmax", dataset="mnist", clients=10, poisoned=0, iters=2000, batch=10, lr=1e-3, momentum=0.75,
-        weight_decay=1e-3, eval_every=100, dp_epsilon=0.0, seed=0, device=None, verbose=True, loss="ce") -> dict:
+        weight_decay=1e-3, eval_every=100, dp_epsilon=0.0, seed=0, device=None, verbose=True, loss="ce",
+        hidden=32) -> dict:
+    if model == "mlp":
+        if loss != "ce" or dp_epsilon > 0:
+            raise ValueError("--model mlp trains under cross-entropy without DP noise (k_mlp_step)")
+        dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
+        return _run_mlp(dataset, clients, poisoned, iters, batch, lr, momentum, weight_decay, eval_every, seed, dev,
+                        verbose, hidden)
     # loss "margin": the reference's commented-out criterion (nn.MultiLabelMarginLoss, client.py:28) with each
     # row's single target, == F.multi_margin_loss; --model svm --loss margin is the reference's SVM
     per_sample = {"ce": F.cross_entropy, "margin": F.multi_margin_loss}[loss]
@@ -114,7 +163,10 @@ def run(model="softmax", dataset="mnist", clients=10, poisoned=0, iters=2000, ba
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="biscotti_amd.sandbox", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mnist_cnn", "lfw_cnn", "cifar_cnn"])
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp", "mnist_cnn", "lfw_cnn", "cifar_cnn"],
+                    help="mlp: a one-hidden-layer ReLU MLP on the project's own kernels (k_mlp_step, k_mlp_eval)")
+    ap.add_argument("--mlp-hidden", type=int, default=32, metavar="H",
+                    help="hidden units of --model mlp: a multiple of 16 in 16..64")
     ap.add_argument("--loss", default="ce", choices=["ce", "margin"],
                     help="training criterion: cross-entropy, or the multi-class margin loss (--model svm --loss margin "
                          "is the reference's SVM)")
@@ -131,7 +183,7 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     res = run(a.model, a.dataset, a.clients, a.poisoned, a.iters, a.batch, a.lr, a.momentum, 1e-3, a.eval_every,
-              a.dp_epsilon, a.seed, a.device, loss=a.loss)
+              a.dp_epsilon, a.seed, a.device, loss=a.loss, hidden=a.mlp_hidden)
     print(json.dumps({k: v for k, v in res.items() if k != "history"}))
     return 0
 

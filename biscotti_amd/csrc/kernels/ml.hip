@@ -5,6 +5,7 @@
 //       (ML/Pytorch/client.py:38-65, client_obj.py:73-77, DistSys/kyber.go:698-710); the same body under the
 //       multi-class margin loss is the SVM task's step (k_margin_step; svm_model.py, client.py:28)
 //   K1m the same step of a one-hidden-layer ReLU MLP (k_mlp_step; FedSys only), K2m its evaluation (k_mlp_eval)
+//   K1c the same step of the MNIST CNN, conv5x5 + ReLU + fc (k_cnn_step; FedSys only), K2c its evaluation (k_cnn_eval)
 //   K1t top-k sparsification of the step's rows: per-row radix select on the fp32 magnitudes, in place
 //       (ML/code/linear_model.py:48-88)
 //   K3  batched logistic-regression step with DP noise at source (ML/code/logistic_model.py:92-140)
@@ -563,6 +564,355 @@ __global__ void __launch_bounds__(256) k_mlp_step(const float* X, const int* y, 
           }
         }
       }
+    }
+  }
+}
+
+// =====================================================================================
+// K1c: local step of the MNIST CNN (mnist_cnn_model.py): x (S x S, S <= 28) -> z = conv5x5(x, padding 4) + bc, 16
+// channels on Q x Q positions (Q = S + 4, NP = Q^2 <= 1024) -> a = relu(z) -> logits = Wfc a + bfc, under
+// cross-entropy.  D_OUT <= 16, B <= 16.  W fp64, flat in torch's parameters() order: [conv.weight (16 x 25) |
+// conv.bias (16) | fc.weight (D_OUT x F, F = 16 NP, feature c NP + oy Q + ox) | fc.bias (D_OUT)].  The draw, the
+// transform, a shard shorter than B, the clip of the whole gradient, the quantisation and the loss are K1's;
+// delta = -lr * clipped gradient.  One 256-thread workgroup per peer; the 1 MB activation map never exists: it is
+// recomputed per position in each of the three passes from the images in LDS.
+//   images   the minibatch's 16 images are staged once, transformed, rows >= Bq zero, one image IS = S^2 | 1 floats
+//            apart (odd: the 16 samples of an operand fall into 16 banks); X is not read again
+//   tile     one output position, all 16 samples and 16 channels: f32 MFMA 16x16x4 over K = the 25 taps padded to 28
+//            (7 k steps).  The lane (i, kk) holds conv.weight[channel i][tap 4 st + kk] in registers for the whole
+//            kernel and gathers pixel (sample i, tap 4 st + kk) from LDS, 0 outside the image (the zero padding).
+//            Weights as A and pixels as B give z[channel 4 kk + r][sample i]; swapped they give
+//            z[sample 4 kk + r][channel i]: the same registers, either layout
+//   k order  an accumulator register is used as the next MFMA's operand without a transpose: k step r of the next
+//            product takes k = (kk; r), i.e. index 4 kk + r, and the other operand is loaded in that order
+//   forward  channel-major tiles: logits^T += Wfc[:, tile] a (K = channels) and the Gram A A^T += a^T a of the
+//            samples' activations, from the same registers
+//   middle   the loss rows (K1's CrossEntropyLoss), G, dbfc, and the fc block's share of the squared norm,
+//            sum_st (G G^T)_st (A A^T)_st, one term per thread
+//   conv     sample-major tiles: dA = G Wfc[:, tile] masked by a > 0, dbc, and dWconv^T += patch^T dA (M = taps in
+//            two tiles of 16, N = channels, K = samples), per-wave accumulators reduced once
+//   clip     the three small blocks' squares join the fc term in fp64, fixed order: the coefficient is known before
+//            dWfc exists
+//   write    sample-major tiles a third time: dWfc[:, tile] = G^T a (K = samples), scaled by -lr * coef into the
+//            wave's stage buffer; after 16 positions the buffer's rows (class, channel) leave as 16 consecutive
+//            entries each: delta and qdelta are written once, in 64 B / 128 B pieces
+//   Wfc      the same stage buffer brings Wfc in for the forward and conv passes: per block of 16 positions each
+//            (class, channel) row is read as one 128 B line of fp64 and kept as fp32
+// The waves deal the blocks of 16 positions round-robin (block b on wave b & 3; all waves run the same number of
+// iterations, so the barriers are uniform); per-wave partials are combined as (0 + 1) + (2 + 3).
+// LDS (bytes): dynamic 16 * 785 * 4 = 50240 of images + 4 * 256 * 17 * 4 = 69632 of stage buffers (rows 17 floats
+// apart) = 119872; static 8192 partials + 256 bias partials + 1024 G + 1728 small gradient + 296 = 11496 (the
+// compiler's figure is in docs/PERF.md).  131368 in all: past the default 64 KiB, inside gfx950's 160 KiB; the
+// launcher raises the dynamic limit once (hipFuncSetAttribute).
+// No atomics, no reduction whose order depends on timing: two runs give the same bytes.
+// =====================================================================================
+constexpr int CNN_SMAX = 28;
+constexpr int CNN_IMG = 16 * (CNN_SMAX * CNN_SMAX + 1);   // floats of the image area
+constexpr int CNN_TS = 17;                                // floats between two rows of a stage buffer
+constexpr int CNN_STAGE = 256 * CNN_TS;                   // floats of one wave's stage buffer
+constexpr int CNN_DYN_LDS = (CNN_IMG + 4 * CNN_STAGE) * (int)sizeof(float);
+
+namespace {
+struct CnnLane {   // what lane (i, kk) keeps for the whole kernel, per k step st: tap t = 4 st + kk
+  float w[7];      // conv.weight[channel i][t], 0 past tap 24
+  int dy[7], dx[7];  // the tap's offset from the output position into the unpadded image; far outside past tap 24
+};
+
+__device__ __forceinline__ CnnLane cnn_lane(const double* Wc) {
+  const int lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
+  CnnLane L;
+#pragma unroll
+  for (int st = 0; st < 7; ++st) {
+    const int t = st * 4 + kk;
+    L.w[st] = t < 25 ? (float)Wc[i * 25 + t] : 0.f;
+    L.dy[st] = t < 25 ? t / 5 - 4 : -64;
+    L.dx[st] = t % 5 - 4;
+  }
+  return L;
+}
+
+// pixel (iy, ix) of the image at im, 0 outside it; the address stays inside the image either way
+__device__ __forceinline__ float cnn_px(const float* im, int S, int iy, int ix) {
+  const bool in = (unsigned)iy < (unsigned)S && (unsigned)ix < (unsigned)S;
+  const float v = im[in ? iy * S + ix : 0];
+  return in ? v : 0.f;
+}
+
+// rows rowidx[0, 16) of X (< 0: a zero image) as (x - tsub) * tmul, image s at img + s * IS
+__device__ __forceinline__ void cnn_stage_images(float* img, const float* X, const long long* rowidx, int S, int IS,
+                                                 float tsub, float tmul) {
+  const int d_in = S * S;
+  for (int e = threadIdx.x; e < 16 * d_in; e += 256) {
+    const int s = e / d_in, k = e - s * d_in;
+    const long long r = rowidx[s];
+    img[s * IS + k] = r >= 0 ? (X[r * (long long)d_in + k] - tsub) * tmul : 0.f;
+  }
+}
+
+// the pre-activations of position (oy, ox) without the bias.  SAMPLES_M: z[sample 4 kk + r][channel i], else
+// z[channel 4 kk + r][sample i].  im: the image of sample i
+template <bool SAMPLES_M>
+__device__ __forceinline__ f32x4 cnn_conv_tile(const float* im, int S, int oy, int ox, const CnnLane& L) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int st = 0; st < 7; ++st) {
+    const float pv = cnn_px(im, S, oy + L.dy[st], ox + L.dx[st]);
+    acc = SAMPLES_M ? __builtin_amdgcn_mfma_f32_16x16x4f32(pv, L.w[st], acc, 0, 0, 0)
+                    : __builtin_amdgcn_mfma_f32_16x16x4f32(L.w[st], pv, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// Wfc[class][c NP + pos0 + p], p < bw <= 16, into this wave's stage buffer as fp32: row class * 16 + c
+// (CLASS_MAJOR) or c * 16 + class, p along the row.  A (class, c) row is 16 lanes' consecutive fp64
+template <bool CLASS_MAJOR>
+__device__ __forceinline__ void cnn_stage_wfc(float* stg, const double* Wfc, int NP, int D_OUT, int pos0, int bw) {
+  const int lane = threadIdx.x & 63, p = lane & 15;
+  for (int q = lane >> 4; q < 16 * D_OUT; q += 4) {
+    const int cls = q >> 4, c = q & 15;
+    if (p < bw)
+      stg[(CLASS_MAJOR ? q : c * 16 + cls) * CNN_TS + p] = (float)Wfc[((size_t)cls * 16 + c) * NP + pos0 + p];
+  }
+}
+
+// The forward pass over every position: this wave's partial logits^T (accl[r] = [class 4 kk + r][sample i]) and,
+// with GRAM, its partial A A^T (accg[r] = [sample 4 kk + r][sample i]).  rows: samples >= rows count as absent
+template <bool GRAM>
+__device__ __forceinline__ void cnn_forward(const float* img, float* stg, int S, const double* Wfc, const double* bc,
+                                            int D_OUT, int rows, const CnnLane& L, f32x4& accl, f32x4& accg) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, i = lane & 15, kk = lane >> 4;
+  const int Q = S + 4, NP = Q * Q, IS = (S * S) | 1;
+  const int iters = ((NP + 15) / 16 + 3) / 4;
+  const float* im = img + i * IS;
+  float bcq[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) bcq[r] = (float)bc[kk * 4 + r];
+  for (int it = 0; it < iters; ++it) {
+    const int pos0 = (it * 4 + wid) * 16, bw = min(16, NP - pos0);   // bw <= 0: no block left for this wave
+    cnn_stage_wfc<false>(stg, Wfc, NP, D_OUT, pos0, bw);
+    __syncthreads();
+    for (int p = 0; p < bw; ++p) {
+      const int pos = pos0 + p, oy = pos / Q, ox = pos - oy * Q;
+      const f32x4 z = cnn_conv_tile<false>(im, S, oy, ox, L);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = z[r] + bcq[r];
+        const float a = (i < rows && v > 0.f) ? v : 0.f;                                  // [channel 4 kk + r][sample i]
+        const float wf = i < D_OUT ? stg[((kk * 4 + r) * 16 + i) * CNN_TS + p] : 0.f;     // Wfc[class i][that channel]
+        accl = __builtin_amdgcn_mfma_f32_16x16x4f32(wf, a, accl, 0, 0, 0);
+        if (GRAM) accg = __builtin_amdgcn_mfma_f32_16x16x4f32(a, a, accg, 0, 0, 0);
+      }
+    }
+    __syncthreads();   // the block has been consumed: the buffer may be filled again
+  }
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) k_cnn_step(const float* X, const int* y, const long long* off,
+                                                             const int* ntrain, const int* pid, const double* W, int S,
+                                                             int D_OUT, int B, int P, unsigned long long seed,
+                                                             int iteration, float max_norm, double qscale, float lr,
+                                                             float* delta, long long* qdelta, float* loss, int lo) {
+  extern __shared__ float cnn_lds[];    // images [16][IS], then one stage buffer per wave
+  __shared__ float red[4][2][16][16];   // per-wave partials: logits^T and A A^T, later the two tap tiles of dWconv^T
+  __shared__ float redb[4][16];         // per-wave partials of dbc
+  __shared__ float G[16][16];           // d(mean loss) / d(logits)
+  __shared__ float gs[416 + 16];        // the raw [dWconv | dbc | dbfc]
+  __shared__ float rowloss[16];
+  __shared__ long long rowidx[16];
+  __shared__ int bidx[16];
+  __shared__ double nrm[4];
+  __shared__ float scale_sh;
+  const int p = blockIdx.x;
+  if (p >= P) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i = lane & 15, kk = lane >> 4;
+  const int Q = S + 4, NP = Q * Q, IS = (S * S) | 1, F = 16 * NP;
+  const double *bc = W + 400, *Wfc = W + 416, *bfc = Wfc + (size_t)D_OUT * F;
+  const size_t nparam = 416 + (size_t)D_OUT * F + D_OUT;
+  float* img = cnn_lds;
+  float* stg = cnn_lds + CNN_IMG + wid * CNN_STAGE;
+  const int li = lo >= 0 ? pid[p] - lo : p;
+  const long long offp = off[li];
+  const int n = ntrain[li];
+  // 1. K1's draw: B distinct minibatch indices from the same Philox counters
+  if (tid == 0) {
+    int cnt = 0;
+    uint32_t ctr = 0;
+    while (cnt < B && cnt < n) {
+      u4 r = philox(u4{(uint32_t)pid[p], (uint32_t)iteration, ctr++, 0x5EEDu}, (uint32_t)seed, (uint32_t)(seed >> 32));
+      const uint32_t cand[4] = {r.x, r.y, r.z, r.w};
+      for (int q = 0; q < 4 && cnt < B && cnt < n; ++q) {
+        const int c = (int)(cand[q] % (uint32_t)n);
+        bool dup = false;
+        for (int t = 0; t < cnt; ++t) dup |= bidx[t] == c;
+        if (!dup) bidx[cnt++] = c;
+      }
+    }
+    for (int t = 0; t < 16; ++t) rowidx[t] = t < cnt ? offp + bidx[t] : -1;
+  }
+  __syncthreads();
+  const int Bq = min(B, n);
+  cnn_stage_images(img, X, rowidx, S, IS, 0.5f, 2.0f);
+  const CnnLane L = cnn_lane(W);
+  __syncthreads();
+  // 2. forward: the logits and the Gram of the activations, per wave, then in LDS
+  {
+    f32x4 accl = {0.f, 0.f, 0.f, 0.f}, accg = {0.f, 0.f, 0.f, 0.f};
+    cnn_forward<true>(img, stg, S, Wfc, bc, D_OUT, Bq, L, accl, accg);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      red[wid][0][kk * 4 + r][i] = accl[r];
+      red[wid][1][kk * 4 + r][i] = accg[r];
+    }
+  }
+  __syncthreads();
+  // 3. the loss and its gradient with respect to the logits on rows s < Bq (one thread per row)
+  if (tid < 16) {
+    const int s = tid;
+    float l = 0.f;
+    if (s < Bq) {
+      float lr_[16];
+      for (int c = 0; c < D_OUT; ++c)
+        lr_[c] = (red[0][0][c][s] + red[1][0][c][s]) + (red[2][0][c][s] + red[3][0][c][s]) + (float)bfc[c];
+      l = CrossEntropyLoss::row(lr_, D_OUT, y[rowidx[s]], Bq, G[s]);
+      for (int c = D_OUT; c < 16; ++c) G[s][c] = 0.f;
+    } else {
+      for (int c = 0; c < 16; ++c) G[s][c] = 0.f;
+    }
+    rowloss[s] = l;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float l = 0.f;
+    for (int s = 0; s < Bq; ++s) l += rowloss[s];
+    loss[p] = l / (float)max(Bq, 1);
+  }
+  if (tid < D_OUT) {
+    float db = 0.f;
+    for (int s = 0; s < 16; ++s) db += G[s][tid];
+    gs[416 + tid] = db;
+  }
+  // the fc block's share of the squared norm: ||G^T A||_F^2 = sum_st (G G^T)_st (A A^T)_st, one term per thread
+  double part;
+  {
+    const int s = tid >> 4, t = tid & 15;
+    float gg = 0.f;
+    for (int c = 0; c < 16; ++c) gg += G[s][c] * G[t][c];
+    const float aa = (red[0][1][s][t] + red[1][1][s][t]) + (red[2][1][s][t] + red[3][1][s][t]);
+    part = (double)gg * (double)aa;
+  }
+  __syncthreads();   // red is free again
+  // 4. the conv gradient: sample-major tiles, dA = G Wfc masked by a > 0, dbc and dWconv^T = patch^T dA
+  {
+    float ga[4];   // G[sample i][class 4 st + kk]
+#pragma unroll
+    for (int st = 0; st < 4; ++st) ga[st] = G[i][st * 4 + kk];
+    const float bci = (float)bc[i];
+    const int t1 = 16 + i;   // the second tap tile's tap of this lane (as A's row)
+    const int dy0 = i / 5 - 4, dx0 = i % 5 - 4, dy1 = t1 < 25 ? t1 / 5 - 4 : -64, dx1 = t1 % 5 - 4;
+    const float* im = img + i * IS;
+    f32x4 aw0 = {0.f, 0.f, 0.f, 0.f}, aw1 = {0.f, 0.f, 0.f, 0.f};
+    float dbs = 0.f;
+    const int iters = ((NP + 15) / 16 + 3) / 4;
+    for (int it = 0; it < iters; ++it) {
+      const int pos0 = (it * 4 + wid) * 16, bw = min(16, NP - pos0);
+      cnn_stage_wfc<true>(stg, Wfc, NP, D_OUT, pos0, bw);
+      __syncthreads();
+      for (int q = 0; q < bw; ++q) {
+        const int pos = pos0 + q, oy = pos / Q, ox = pos - oy * Q;
+        const f32x4 z = cnn_conv_tile<true>(im, S, oy, ox, L);
+        f32x4 da = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+          const int cls = st * 4 + kk;
+          const float wf = cls < D_OUT ? stg[(cls * 16 + i) * CNN_TS + q] : 0.f;   // Wfc[class][channel i]
+          da = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[st], wf, da, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int s = kk * 4 + r;
+          const float dz = (s < Bq && z[r] + bci > 0.f) ? da[r] : 0.f;   // [sample 4 kk + r][channel i]
+          dbs += dz;
+          const float* ims = img + s * IS;
+          aw0 = __builtin_amdgcn_mfma_f32_16x16x4f32(cnn_px(ims, S, oy + dy0, ox + dx0), dz, aw0, 0, 0, 0);
+          aw1 = __builtin_amdgcn_mfma_f32_16x16x4f32(cnn_px(ims, S, oy + dy1, ox + dx1), dz, aw1, 0, 0, 0);
+        }
+      }
+      __syncthreads();
+    }
+    dbs += __shfl_xor(dbs, 16);
+    dbs += __shfl_xor(dbs, 32);
+    if (kk == 0) redb[wid][i] = dbs;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {   // [tap 4 kk + r (+ 16)][channel i]
+      red[wid][0][kk * 4 + r][i] = aw0[r];
+      red[wid][1][kk * 4 + r][i] = aw1[r];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < 416; e += 256) {
+    if (e < 400) {
+      const int ch = e / 25, t = e - ch * 25, h = t >> 4, tt = t & 15;
+      gs[e] = (red[0][h][tt][ch] + red[1][h][tt][ch]) + (red[2][h][tt][ch] + red[3][h][tt][ch]);
+    } else {
+      gs[e] = (redb[0][e - 400] + redb[1][e - 400]) + (redb[2][e - 400] + redb[3][e - 400]);
+    }
+  }
+  __syncthreads();
+  // 5. clip_grad_norm(max_norm) over all four parameter blocks, before dWfc exists
+  for (int e = tid; e < 416 + D_OUT; e += 256) part += (double)gs[e] * (double)gs[e];
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+  if (lane == 0) nrm[wid] = part;
+  __syncthreads();
+  if (tid == 0) {
+    const float tot = sqrtf((float)fmax((nrm[0] + nrm[1]) + (nrm[2] + nrm[3]), 0.0));
+    const float coef = max_norm / (tot + 1e-6f);
+    scale_sh = coef < 1.f ? coef : 1.f;
+  }
+  __syncthreads();
+  // 6. delta = -lr * clipped gradient, quantised like updateFloatToInt: the small blocks, then dWfc block by block
+  const float sc = -lr * scale_sh;
+  float* dst = delta + (size_t)p * nparam;
+  long long* qd = qdelta + (size_t)p * nparam;
+  for (int e = tid; e < 416 + D_OUT; e += 256) {
+    const float v = gs[e] * sc;
+    const size_t at = e < 416 ? (size_t)e : 416 + (size_t)D_OUT * F + (e - 416);
+    dst[at] = v;
+    qd[at] = quantize(v, qscale);
+  }
+  {
+    float gw[4];   // G[sample 4 kk + r][class i]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) gw[r] = G[kk * 4 + r][i];
+    const float bci = (float)bc[i];
+    const float* im = img + i * IS;
+    const int iters = ((NP + 15) / 16 + 3) / 4;
+    for (int it = 0; it < iters; ++it) {
+      const int pos0 = (it * 4 + wid) * 16, bw = min(16, NP - pos0);
+      for (int q = 0; q < bw; ++q) {
+        const int pos = pos0 + q, oy = pos / Q, ox = pos - oy * Q;
+        const f32x4 z = cnn_conv_tile<true>(im, S, oy, ox, L);
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = z[r] + bci;
+          const float a = (kk * 4 + r < Bq && v > 0.f) ? v : 0.f;   // [sample 4 kk + r][channel i]
+          o = __builtin_amdgcn_mfma_f32_16x16x4f32(gw[r], a, o, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) stg[((kk * 4 + r) * 16 + i) * CNN_TS + q] = o[r] * sc;   // [class 4 kk + r][channel i]
+      }
+      __syncthreads();
+      const int pp = lane & 15;
+      if (pp < bw) {
+        for (int q = lane >> 4; q < 16 * D_OUT; q += 4) {   // row q = (class, channel): 16 consecutive entries
+          const size_t at = 416 + (size_t)q * NP + pos0 + pp;
+          const float v = stg[q * CNN_TS + pp];
+          dst[at] = v;
+          qd[at] = quantize(v, qscale);
+        }
+      }
+      __syncthreads();
     }
   }
 }
@@ -2537,6 +2887,53 @@ __global__ void __launch_bounds__(256) k_mlp_eval(const float* X, const int* y, 
   }
 }
 
+// K2c: the same two miss counts for K1c's CNN (W in its layout).  One block per 16 rows on the step's forward body
+// (cnn_forward without the Gram): the rows' images staged once with the transform fused, the per-wave partial
+// logits combined in LDS in the step's order, then one thread per row takes the argmax (first maximum) and wave 0
+// counts the misses of either set by ballot: at most two integer atomics per block.  LDS: K1c's 119872 dynamic bytes
+// + 4096 partials + 128.
+extern "C" __global__ void __launch_bounds__(256) k_cnn_eval(const float* X, const int* y, int N, int S, int D_OUT,
+                                                             const double* W, int transform, int split,
+                                                             unsigned int* err) {
+  extern __shared__ float cnn_lds[];
+  __shared__ float red[4][16][16];
+  __shared__ long long rowidx[16];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i = lane & 15, kk = lane >> 4;
+  const int row0 = blockIdx.x * 16, NP = (S + 4) * (S + 4);
+  const double *bc = W + 400, *Wfc = W + 416, *bfc = Wfc + (size_t)D_OUT * 16 * NP;
+  if (tid < 16) rowidx[tid] = row0 + tid < N ? row0 + tid : -1;
+  __syncthreads();
+  cnn_stage_images(cnn_lds, X, rowidx, S, (S * S) | 1, transform ? 0.5f : 0.f, transform ? 2.f : 1.f);
+  const CnnLane L = cnn_lane(W);
+  __syncthreads();
+  f32x4 accl = {0.f, 0.f, 0.f, 0.f}, unused = {0.f, 0.f, 0.f, 0.f};
+  cnn_forward<false>(cnn_lds, cnn_lds + CNN_IMG + wid * CNN_STAGE, S, Wfc, bc, D_OUT, 16, L, accl, unused);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[wid][kk * 4 + r][i] = accl[r];
+  __syncthreads();
+  if (tid >= 64) return;
+  const int row = row0 + tid;
+  bool miss = false;
+  if (tid < 16 && row < N) {
+    float bv = -__builtin_huge_valf();
+    int bcl = 0;
+    for (int c = 0; c < D_OUT; ++c) {
+      const float v = (red[0][c][tid] + red[1][c][tid]) + (red[2][c][tid] + red[3][c][tid]) + (float)bfc[c];
+      if (v > bv) {
+        bv = v;
+        bcl = c;
+      }
+    }
+    miss = bcl != y[row];
+  }
+  const unsigned int cnt0 = (unsigned int)__popcll(__ballot(miss && row < split));
+  const unsigned int cnt1 = (unsigned int)__popcll(__ballot(miss && row >= split));
+  if (tid == 0) {
+    if (cnt0) atomicAdd(err, cnt0);
+    if (cnt1) atomicAdd(err + 1, cnt1);
+  }
+}
+
 // =====================================================================================
 // Committee RONI (VerifyUpdateRONI, main.go:191-233): every local verifier's minibatch scored under the base
 // model and under W + U[c] for every row c of its inbox, in ONE launch.  counts[v][0] = #misclassified
@@ -2969,6 +3366,23 @@ extern "C" int bsc_mlp_step(const float* X, const int* y, const long long* off, 
   return (int)hipGetLastError();
 }
 
+// K1c: bsc_softmax_step's arguments and limits with the image side S (1..28, D_IN = S * S) in D_IN's place, W in the
+// CNN's layout and the step rate lr > 0 behind qscale; no speculative row flags (the ledger does not run this model)
+extern "C" int bsc_cnn_step(const float* X, const int* y, const long long* off, const int* ntrain, const int* pid,
+                            const double* W, int S, int D_OUT, int B, int P, unsigned long long seed, int iteration,
+                            float max_norm, double qscale, float lr, float* delta, long long* qdelta, float* loss,
+                            int lo, void* stream) {
+  if (S < 1 || S > CNN_SMAX || D_OUT < 1 || D_OUT > 16 || B > 16 || !(lr > 0.f)) return -1;
+  if (P <= 0) return 0;
+  // K1c's images and stage buffers pass the default 64 KiB of LDS: opt in once
+  static const hipError_t optin =
+      hipFuncSetAttribute((const void*)k_cnn_step, hipFuncAttributeMaxDynamicSharedMemorySize, CNN_DYN_LDS);
+  if (optin != hipSuccess) return (int)optin;
+  hipLaunchKernelGGL(k_cnn_step, dim3(P), dim3(256), CNN_DYN_LDS, (hipStream_t)stream, X, y, off, ntrain, pid, W, S,
+                     D_OUT, B, P, seed, iteration, max_norm, qscale, lr, delta, qdelta, loss, lo);
+  return (int)hipGetLastError();
+}
+
 namespace {
 template <class Loss>
 int local_steps_launch(hipStream_t s, int nparam, const float* X, const int* y, const long long* off, const int* ntrain,
@@ -3347,6 +3761,20 @@ extern "C" int bsc_mlp_eval_rb(const float* X, const int* y, int N, int D_IN, in
     }
 #undef BSC_MLP_EVAL
   }
+  hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, err, err_host);
+  return (int)hipGetLastError();
+}
+
+// K2c with the same hand-off; S as in bsc_cnn_step
+extern "C" int bsc_cnn_eval_rb(const float* X, const int* y, int N, int S, int D_OUT, const double* W, int transform,
+                               int split, unsigned int* err, unsigned int* err_host, void* stream) {
+  if (S < 1 || S > CNN_SMAX || D_OUT < 1 || D_OUT > 16) return -1;
+  static const hipError_t optin =
+      hipFuncSetAttribute((const void*)k_cnn_eval, hipFuncAttributeMaxDynamicSharedMemorySize, CNN_DYN_LDS);
+  if (optin != hipSuccess) return (int)optin;
+  if (N > 0)
+    hipLaunchKernelGGL(k_cnn_eval, dim3((N + 15) / 16), dim3(256), CNN_DYN_LDS, (hipStream_t)stream, X, y, N, S, D_OUT,
+                       W, transform, split, err);
   hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, err, err_host);
   return (int)hipGetLastError();
 }

@@ -21,10 +21,11 @@ def build_parser() -> argparse.ArgumentParser:
     add_framework_flags(ap)
     ap.set_defaults(perc_samples=35, epsilon=5.0)
     ap.add_argument("--rounds", type=int, default=None)
-    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp"],
-                    help="softmax regression, svm: the same linear scorer under the multi-class margin loss, or mlp: a "
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp", "mnist_cnn"],
+                    help="softmax regression, svm: the same linear scorer under the multi-class margin loss, mlp: a "
                          "one-hidden-layer ReLU MLP under cross-entropy (k_mlp_step; the plain single step only) "
-                         "(mnist and lfw)")
+                         "(mnist and lfw), or mnist_cnn: the reference's Conv(1->16, 5x5) + ReLU + Linear CNN "
+                         "(k_cnn_step; mnist only, the plain single step at rate --local-lr)")
     ap.add_argument("--mlp-hidden", type=int, default=32, metavar="H",
                     help="hidden units of --model mlp: a multiple of 16 in 16..64")
     ap.add_argument("--topk", type=float, default=1.0, metavar="THETA",

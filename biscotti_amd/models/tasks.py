@@ -237,6 +237,42 @@ class MlpTask(SoftmaxTask):
         raise NotImplementedError("RONI scores the ledger's linear models; the MLP runs under FedSys only")
 
 
+class CnnTask(SoftmaxTask):
+    """SoftmaxTask's data under the MNIST CNN, Conv(1 -> 16, 5x5, padding 4) + ReLU + Linear (K.cnn_step /
+    K.cnn_errors_async; docs/QUIRKS.md Q22), every peer's step scaled by `lr`.  FedSys only, like MlpTask."""
+
+    def __init__(self, peers: range, num_peers: int, device, seed: int, lr: float = 1.0, **kw):
+        super().__init__(peers, num_peers, device, seed, **kw)
+        self.lr = float(lr)
+        self.nparam = K.cnn_nparam(self.d_in, self.d_out)   # raises on a shape the kernels do not take
+
+    def initial_model(self) -> torch.Tensor:
+        """The model of round 0, the same on every rank (K.cnn_init under the run's seed)."""
+        return K.cnn_init(self.d_in, self.d_out, self.seed).to(self.device)
+
+    def step(self, W: torch.Tensor, iteration: int, peers: list[int]):
+        if not peers:
+            z = torch.empty((0, self.nparam), device=self.device)
+            return z.float(), z.long()
+        pid = h2d(peers, torch.int32, self.device)
+        delta, qdelta, self.last_loss = K.cnn_step(self.X, self.y, self.off, self.ntrain, pid, W, self.d_in, self.d_out,
+                                                   self.batch, self.seed, iteration, 100.0, 1e4, lo=self.peers[0],
+                                                   lr=self.lr)
+        return delta, qdelta
+
+    def evaluate_async(self, W: torch.Tensor):
+        both = K.cnn_errors_async(self.eval_X, self.eval_y, self.eval_split, W, self.d_in, self.d_out)
+
+        def result():
+            err, att = both()
+            return {"test_error": err, "attack_rate": att}
+        result.ready = both.ready
+        return result
+
+    def train_error(self, W: torch.Tensor, peer: int, iteration: int) -> float:
+        raise NotImplementedError("RONI scores the ledger's linear models; the CNN runs under FedSys only")
+
+
 class LogisticTask:
     """creditcard logistic regression: every peer loads the full dataset (logistic_model.py:26)."""
 
@@ -361,9 +397,9 @@ MODELS = ("softmax", "svm")   # the ledger's linear models: what --model takes
 
 
 def ledger_model(model: str) -> str:
-    """`model` for a ledger engine or tool: the MLP has no place there yet."""
-    if model == "mlp":
-        raise ValueError("model 'mlp': FedSys only for now: the ledger's d, pre-step and genesis model are linear")
+    """`model` for a ledger engine or tool: the MLP and the CNN have no place there yet."""
+    if model in ("mlp", "mnist_cnn"):
+        raise ValueError(f"model {model!r}: FedSys only for now: the ledger's d, pre-step and genesis model are linear")
     return model
 
 
@@ -379,7 +415,21 @@ def make_task(dataset: str, peers: range, num_peers: int, device, seed: int, mod
     place of batch_size (SoftmaxTask's lot_size).  local_momentum / local_decay / local_prox > 0: the local steps run
     under heavy-ball momentum, weight decay and a FedProx proximal weight (SoftmaxTask's local_momentum).
     model "mlp" (FedSys only, not one of MODELS): mnist / lfw under a one-hidden-layer ReLU MLP of `hidden` units
-    (MlpTask), the plain single step only."""
+    (MlpTask), the plain single step only.  model "mnist_cnn" (FedSys only, not one of MODELS): mnist under the
+    reference's conv + fc CNN (CnnTask), the plain single step at rate local_lr."""
+    if model == "mnist_cnn":
+        if dataset != "mnist":
+            raise ValueError(f"model 'mnist_cnn' is mnist's 28 x 28 CNN: {dataset} has no kernel for its own")
+        if topk != 1.0 or local_steps != 1 or dp_clip != 0 or dp_sigma != 0 or lot_size != 0 or \
+                local_momentum != 0 or local_decay != 0 or local_prox != 0:
+            raise ValueError("model 'mnist_cnn' takes the plain single step (at rate local_lr): topk, local_steps, "
+                             "dp_clip / dp_sigma, lot_size and local_momentum / local_decay / local_prox are kernels of "
+                             "the linear scorer only")
+        if not local_lr > 0:
+            raise ValueError(f"local_lr is positive, not {local_lr!r}")
+        for k in ("epsilon", "colluders"):
+            kw.pop(k, None)
+        return CnnTask(peers, num_peers, device, seed, lr=local_lr, **kw)
     if model == "mlp":
         if dataset not in ("mnist", "lfw"):
             raise ValueError("model 'mlp' needs a multi-class dataset (mnist, lfw): creditcard trains its logistic model")

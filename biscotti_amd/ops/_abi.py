@@ -58,6 +58,8 @@ SIGNATURES = {
     "bsc_margin_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, P, P, P, I, P, I, P],
     "bsc_mlp_step": [P, P, P, P, P, P, I, I, I, I, I, U64, I, F, D, P, P, P, I, P],
     "bsc_mlp_eval_rb": [P, P, I, I, I, I, P, I, I, P, P, P],
+    "bsc_cnn_step": [P, P, P, P, P, P, I, I, I, I, U64, I, F, D, F, P, P, P, I, P],
+    "bsc_cnn_eval_rb": [P, P, I, I, I, P, I, I, P, P, P],
     "bsc_local_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, I, F, P, P, P, I, P, I, P],
     "bsc_dpsgd_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, D, F, F, I, F, P, P, P, I, P, I, P],
     "bsc_lot_steps": [I, P, P, P, P, P, P, I, I, I, I, U64, I, F, D, F, F, I, F, P, P, P, P, I, P, I, P],

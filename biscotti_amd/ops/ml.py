@@ -302,6 +302,128 @@ def mlp_errors_async(X, y, split: int, W, d_in, H, d_out, transform=True):
     return result
 
 
+# ---------------------------------------------------------------------------- K1c / K2c the MNIST CNN
+def _cnn_side(d_in: int, d_out: int) -> int:
+    """The image side S of d_in = S * S pixels; ValueError on a shape k_cnn_step does not take."""
+    S = math.isqrt(d_in) if d_in == int(d_in) and d_in > 0 else 0
+    if S * S != d_in or not 1 <= S <= 28:
+        raise ValueError(f"the CNN kernels take square images of side 1..28, not {d_in!r} pixels")
+    if not 1 <= d_out <= 16:
+        raise ValueError(f"the CNN kernels take up to 16 classes, not {d_out!r}")
+    return S
+
+
+def cnn_nparam(d_in: int, d_out: int) -> int:
+    """Parameters of Conv(1 -> 16, 5x5, padding 4) + ReLU + Linear(16 (S + 4)^2 -> d_out) on S x S images."""
+    S = _cnn_side(d_in, d_out)
+    return 416 + d_out * 16 * (S + 4) ** 2 + d_out
+
+
+def _cnn_split(Wm, S, d_out):
+    """[conv.weight (16 x 1 x 5 x 5) | conv.bias (16) | fc.weight (d_out x 16 (S + 4)^2) | fc.bias (d_out)]:
+    MNISTCNNModel.parameters()."""
+    F = 16 * (S + 4) ** 2
+    return Wm[:400].view(16, 1, 5, 5), Wm[400:416], Wm[416:416 + d_out * F].view(d_out, F), Wm[416 + d_out * F:]
+
+
+def cnn_init(d_in: int, d_out: int, seed: int) -> torch.Tensor:
+    """The CNN's initial vector, fp64 on the host, in mlp_init's manner: He-uniform weights (bound sqrt(6 / fan_in),
+    fan_in 25 and 16 (S + 4)^2) from the Philox stream of tag 0xC22 under `seed`, zero biases.  A function of its
+    arguments only: the same on every rank.  (All-zero weights are a fixed point of this model too.)"""
+    S = _cnn_side(d_in, d_out)
+    F = 16 * (S + 4) ** 2
+    n = 400 + d_out * F
+    r = philox4x32(np.arange((n + 3) // 4), 0, 0, 0xC22, seed & MASK32, (seed >> 32) & MASK32)
+    u = ((np.stack(r, 1).reshape(-1)[:n] >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0 * 2.0 - 1.0
+    W = np.zeros(cnn_nparam(d_in, d_out))
+    W[:400] = u[:400] * math.sqrt(6.0 / 25)
+    W[416:416 + d_out * F] = u[400:] * math.sqrt(6.0 / F)
+    return torch.from_numpy(W)
+
+
+def cnn_step(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, max_norm=100.0, qscale=1e4, lo=-1, lr=1.0):
+    """softmax_step for the MNIST CNN x -> relu(conv5x5(x, padding 4) + bc) -> Wfc a + bfc under cross-entropy
+    (k_cnn_step): the same minibatch draw, transform, clip of the whole gradient and quantisation, with
+    delta = -lr * clipped gradient.  W fp64 [cnn_nparam], laid out as _cnn_split reads it; d_in = S * S, S <= 28.
+    The other arguments and the return values are softmax_step's."""
+    S = _cnn_side(d_in, d_out)
+    if not lr > 0:
+        raise ValueError(f"the step rate is positive, not {lr!r}")
+    P = pid.numel()
+    nparam = cnn_nparam(d_in, d_out)
+    dev = X.device
+    delta = torch.empty((P, nparam), dtype=torch.float32, device=dev)
+    qdelta = torch.empty((P, nparam), dtype=torch.int64, device=dev)
+    loss = torch.empty((P,), dtype=torch.float32, device=dev)
+    if dev.type == "cuda":
+        assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+        assert off.dtype == torch.int64 and ntrain.dtype == torch.int32 and W.numel() == nparam
+        assert pid.dtype == torch.int32 and (lo >= 0 or off.numel() == P) and X.shape[1] == d_in
+        _check(hip().bsc_cnn_step(_p(X), _p(y), _p(off), _p(ntrain), _p(pid), _p(W), S, d_out, B, P,
+                                  seed & (2**64 - 1), iteration, float(max_norm), float(qscale), float(lr), _p(delta),
+                                  _p(qdelta), _p(loss), int(lo), _stream()), "cnn_step")
+        return delta, qdelta, loss
+    Wc, bc, Wfc, bfc = _cnn_split(W.to(torch.float32), S, d_out)
+    pids = pid.tolist()
+    if lo >= 0:
+        offs = [int(off[q - lo]) for q in pids]
+        ns = [int(ntrain[q - lo]) for q in pids]
+    else:
+        offs, ns = off.tolist(), ntrain.tolist()
+    for p in range(P):
+        idx = minibatch_indices(pids[p], iteration, ns[p], B, seed)
+        rows = torch.tensor([offs[p] + i for i in idx], dtype=torch.long)
+        xb = ((X[rows] - 0.5) / 0.5).view(-1, 1, S, S)
+        z = torch.nn.functional.conv2d(xb, Wc, bc, padding=4)
+        a = torch.relu(z).flatten(1)
+        lossv, g = _ce_rows(a @ Wfc.T + bfc, y[rows].long())
+        dz = ((g @ Wfc) * (a > 0)).view_as(z)
+        dWc = torch.nn.functional.conv2d(xb.transpose(0, 1), dz.transpose(0, 1), padding=4).transpose(0, 1)
+        flat = torch.cat([dWc.reshape(-1), dz.sum((0, 2, 3)), (g.T @ a).reshape(-1), g.sum(0)])
+        coef = max_norm / (float(torch.linalg.vector_norm(flat)) + 1e-6)
+        if coef < 1:
+            flat = flat * coef
+        delta[p] = -lr * flat
+        qdelta[p] = torch.from_numpy((delta[p].double().numpy() * qscale).astype(np.int64))
+        loss[p] = lossv
+    return delta, qdelta, loss
+
+
+def cnn_errors_async(X, y, split: int, W, d_in, d_out, transform=True):
+    """eval_errors_async for the CNN (k_cnn_eval): the error rates of W on rows [0, split) and [split, N) of X from
+    one launch and one read-back.  Returns a callable giving (err_a, err_b), with .ready like eval_errors_async's."""
+    side = _cnn_side(d_in, d_out)
+    N = X.shape[0]
+    na, nb = split, N - split
+    if X.device.type != "cuda":
+        Wc, bc, Wfc, bfc = _cnn_split(W.to(torch.float32), side, d_out)
+        xb = ((X - 0.5) / 0.5 if transform else X).view(-1, 1, side, side)
+        a = torch.relu(torch.nn.functional.conv2d(xb, Wc, bc, padding=4)).flatten(1)
+        miss = torch.argmax(a @ Wfc.T + bfc, 1) != y.long()
+        e = (int(miss[:split].sum()), int(miss[split:].sum()))
+        ready = lambda: True   # noqa: E731
+    else:
+        assert X.dtype == torch.float32 and y.dtype == torch.int32 and W.dtype == torch.float64
+        assert W.numel() == cnn_nparam(d_in, d_out) and 0 <= split <= N and X.shape[1] == d_in
+        host = pinned("cnn_eval", (2,), torch.int32, depth=4)
+        err = _EVAL_DEV.get((host.data_ptr(), "cnn"))   # 3 counters, zero between launches (k_eval_finish)
+        if err is None:
+            err = _EVAL_DEV[(host.data_ptr(), "cnn")] = torch.zeros((4,), dtype=torch.int32, device=X.device)
+        _check(hip().bsc_cnn_eval_rb(_p(X), _p(y), N, side, d_out, _p(W), int(transform), int(split), _p(err),
+                                     host.data_ptr(), _stream()), "cnn_eval")
+        ev = S.record()
+        e, ready = None, ev.query
+
+    def result():
+        c = e
+        if c is None:
+            S.host_wait(ev)
+            c = host.tolist()
+        return (c[0] / na if na else 0.0, c[1] / nb if nb else 0.0)
+    result.ready = ready
+    return result
+
+
 def local_steps(X, y, off, ntrain, pid, W, d_in, d_out, B, seed, iteration, E, lr, loss="ce", max_norm=100.0,
                 qscale=1e4, lo=-1):
     """E local SGD steps per peer at rate lr under loss "ce" or "margin" (k_local_steps): step e differentiates the

@@ -54,11 +54,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device-sign", action="store_true",
                     help="the verifiers' Schnorr signatures from k_schnorr_sign (kernels/schnorr.hip) instead of the "
                          "host's signing pool: the same bytes (engine.sign_device; a CPU engine signs on the host)")
-    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp"],
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp", "mnist_cnn"],
                     help="the ledger's model: softmax regression, or svm -- the same linear scorer under the "
                          "multi-class margin loss (k_margin_step; mnist and lfw).  A chain does not record it: "
-                         "--resume needs the same --model.  mlp is FedSys's (biscotti_amd.fedsys): "
-                         "here it is refused")
+                         "--resume needs the same --model.  mlp and mnist_cnn are FedSys's "
+                         "(biscotti_amd.fedsys): here they are refused")
     ap.add_argument("--topk", type=float, default=1.0, metavar="THETA",
                     help="top-k sparsified updates: every peer keeps the int(d * THETA) largest-magnitude entries of "
                          "its update and zeroes the rest (k_topk_rows; mnist and lfw, 0 < THETA <= 1, 1 = off).  A "

@@ -54,7 +54,8 @@ class FedSysEngine:
 
         self.cfg = cfg
         # "softmax" or "svm" (models.make_task), as BiscottiEngine's; here also "mlp", a one-hidden-layer ReLU MLP of
-        # `hidden` units (docs/QUIRKS.md Q21)
+        # `hidden` units (docs/QUIRKS.md Q21), and "mnist_cnn", the reference's conv + fc CNN on mnist, whose single
+        # step takes local_lr as its rate (Q22)
         self.model, self.hidden = model, hidden
         self.topk = topk     # top-k sparsified updates (models.make_task), as BiscottiEngine's; 1: off
         self.local_steps, self.local_lr = local_steps, local_lr   # local SGD steps per round and their rate; 1: off
@@ -88,7 +89,7 @@ class FedSysEngine:
                               data_dir=cfg.data_dir, epsilon=cfg.epsilon, colluders=set())
         self.d = self.task.nparam
         self.log.info("model %s on %s: %d peers, %d parameters", model, cfg.dataset, self.N, self.d)
-        # a task whose all-zero model cannot train (the MLP) brings its own round-0 model, the same on every rank
+        # a task whose all-zero model cannot train (the MLP, the CNN) brings its own round-0 model, the same on every rank
         init = getattr(self.task, "initial_model", None)
         self.W = init() if init else torch.zeros(self.d, dtype=torch.float64, device=self.dev)
         self.iteration = 0

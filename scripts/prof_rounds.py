@@ -39,7 +39,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--emulate-world", type=int, default=0)
     ap.add_argument("--device-sign", action="store_true")
-    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp"])
+    ap.add_argument("--model", default="softmax", choices=["softmax", "svm", "mlp", "mnist_cnn"])
     ap.add_argument("--topk", type=float, default=1.0)
     ap.add_argument("--local-steps", type=int, default=1)
     ap.add_argument("--local-lr", type=float, default=1.0)
